@@ -24,13 +24,17 @@ per GPU, LOCAL_RANK = GPU ordinal) before touching any GPU; under
 but a gloo barrier and the max-over-ranks time (no data-path collective; the
 control plane does not need RCCL).
 
-Besides the contract fields the JSON line carries
+A plain run sets up, warms up, times the K steps, writes the last step's
+outputs when `--dump-outputs DIR` asks for them, and prints the JSON line.
+Besides the contract fields the line carries
   roofline:     the encode kernels' algorithmic file bytes per launch / their
                 mean duration (HIP events on the kernel stream) against the HBM
-                read peak (vendor 8.0 TB/s; `peak_measured` = hb_stream_read on
-                the same buffer), traffic from the committed rocprofv3 PMC pass
-                when it matches this workload, and the LDS-lookup and VALU
-                resources that actually bind (DESIGN.md);
+                read peak (vendor 8.0 TB/s), traffic from the committed
+                rocprofv3 PMC pass when it matches this workload, and the
+                LDS-lookup and VALU resources that actually bind.
+`--full` adds, after the timed region, `roofline.peak_measured` (hb_stream_read
+on the same buffer), the sustained rate, the prove / wide / configs1 /
+host-memory rows and
   parity_sample: >= 10,000 random blocks plus the first and last 1,000 (the
                 tail block included) of every rank's tags, after the timed
                 region, against the CPU oracle;
@@ -115,6 +119,14 @@ def parse(argv=None):
                          "N = 1 configs[2] run")
     ap.add_argument("--no-configs1", action="store_true",
                     help="skip the `configs1` row (configs[1]: 1 GiB, S = 1) of the default N = 1 configs[2] run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other measurement and check: the measured HBM "
+                         "read peak, the sustained rate, the prove / wide / configs1 / host-memory rows, the parity "
+                         "sample against the oracle and the CPU baselines (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float64; "
+                         "encode: the tags as big-endian 32-bit words, a fixed seeded sample of block runs when "
+                         "there are many, and the PRF try count; prove: mu and sigma)")
     ap.add_argument("--dry-run", action="store_true",
                     help="exercise the launch / rank / timing / JSON plumbing without HIP calls (CPU tests)")
     args = ap.parse_args(argv)
@@ -347,6 +359,7 @@ def bench_encode(args, cfg, R):
     kms_list = []
     wall_sum = 0.0
     for _ in range(args.steps):
+        tries_before = tries_total[0]
         wall, kms = step()
         wall_sum += wall
         kms_list.append(kms)
@@ -355,6 +368,8 @@ def bench_encode(args, cfg, R):
     if len(pieces) > 1:
         elapsed = wall_sum          # refills of the resident piece are not part of the encode
     elapsed = R.reduce(elapsed, "max")
+    if args.dump_outputs:
+        dump_encode(args.dump_outputs, R, ctx, L, tptr, nblocks, w, tries_total[0] - tries_before)
 
     total_bytes = file_len * args.steps
     value = total_bytes / GIB / elapsed
@@ -402,7 +417,7 @@ def bench_encode(args, cfg, R):
     peak_measured = None
     ms = ctypes.c_double()
     nread = piece_bytes // 16 * 16
-    if nread:
+    if nread and args.full:
         for _ in range(2):          # the second pass is the measurement
             ctx.check(L.hb_stream_read(ctx.h, dptr, nread, ctypes.byref(ms)))
         peak_measured = round(nread / (ms.value * 1e-3) / 1e9, 1)
@@ -472,12 +487,13 @@ def bench_encode(args, cfg, R):
         "aes_per_block": round(aes / nblocks, 3),
     }
 
-    if args.sustain_seconds > 0 and len(pieces) == 1:
+    if args.full and args.sustain_seconds > 0 and len(pieces) == 1:
         line["sustained"] = sustained(args, R, step, elapsed / args.steps, file_len)
     # configs[4] on this very file (64 GiB, S = 16, 256-bit prime, its tags
     # just computed): the prove row of the same run, before the host-path rows
     # reuse the device buffer
-    if R.rank == 0 and R.world == 1 and args.config == "c3" and not cxx and not args.no_prove and len(pieces) == 1:
+    if (args.full and R.rank == 0 and R.world == 1 and args.config == "c3" and not cxx and not args.no_prove
+            and len(pieces) == 1):
         t = time.perf_counter()
         line["prove"] = prove_row(ctx, L, dptr, tptr, length, nblocks, S, p, C, w, args, fk, ak,
                                   proofs=args.prove_proofs)
@@ -488,7 +504,7 @@ def bench_encode(args, cfg, R):
     # (profiles/r05/f: bench_c3 vs bench_c3_nocpu), a state of the process's
     # host memory, not of the encode
     want_host = args.host_path or (R.world == 1 and args.config == "c3" and not cxx and not args.single_pass)
-    if R.rank == 0 and want_host and not args.no_host_path:
+    if args.full and R.rank == 0 and want_host and not args.no_host_path:
         t = time.perf_counter()
         line["host_path"] = host_path(ctx, L, dptr, pieces[0][1], S, pb, fk, ak, C)
         line["host_path"]["seconds_spent"] = round(time.perf_counter() - t, 1)
@@ -501,24 +517,24 @@ def bench_encode(args, cfg, R):
     if R.rank == 0 and R.world == 1 and args.config == "c3" and not cxx and len(pieces) == 1:
         aes_rate_c3 = aes / (kernel_ms * 1e-3)
         line["aes_g_per_s"] = round(aes_rate_c3 / 1e9, 2)
-        if not args.no_wide:
+        if args.full and not args.no_wide:
             t = time.perf_counter()
             line["wide"] = extra_encode_row(ctx, L, dptr, min(8 * GIB, length), 1024, 10, fk, ak, args,
                                             steps=5, warmup=2, aes_rate_ref=aes_rate_c3, with_prove=not args.no_prove)
             line["wide"]["seconds_spent"] = round(time.perf_counter() - t, 1)
-        if not args.no_configs1:
+        if args.full and not args.no_configs1:
             t = time.perf_counter()
             line["configs1"] = extra_encode_row(ctx, L, dptr, min(1 * GIB, length), 256, 1, fk, ak, args,
                                                 steps=20, warmup=3, aes_rate_ref=aes_rate_c3)
             line["configs1"]["seconds_spent"] = round(time.perf_counter() - t, 1)
-    if not args.no_parity_sample:
+    if args.full and not args.no_parity_sample:
         ok, n = parity_sample(ctx, L, dptr, tptr, pieces, plan, S, p, fk, ak, C, w, args, cxx, fill)
         n_all = int(R.reduce(n, "sum"))
         ok_all = R.reduce(1.0 if ok else 0.0, "min") == 1.0
         line["parity_sample"] = {"n": n_all, "ok": ok_all,
                                  "what": ">= %d random blocks + first/last 1,000 per rank (tail included) "
                                          "vs oracle/swizzle_oracle.c" % args.parity_blocks}
-    if R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
+    if args.full and R.rank == 0 and R.world == 1 and not args.no_cpu_baseline:
         if len(pieces) > 1:
             fill(0)
         line["cpu_baseline"] = cpu_baseline(ctx, L, dptr, tptr, pieces[0][1], S, p, fk, ak, C,
@@ -528,6 +544,51 @@ def bench_encode(args, cfg, R):
         print(json.dumps(line), flush=True)
     ctx.check(L.hb_device_free(ctx.h, dptr))
     ctx.check(L.hb_device_free(ctx.h, tptr))
+
+
+DUMP_ALL_BLOCKS = 1 << 18     # up to this many tags are dumped whole (16 MiB of float64 at w = 32)
+DUMP_RUNS = 62                # else: the first and last run and this many seeded ones ...
+DUMP_RUN_BLOCKS = 4096        # ... of this many consecutive blocks each
+
+
+def dump_runs(nblocks):
+    """The [b0, b1) block runs of a tag array that --dump-outputs writes, in
+    ascending order: all of it up to DUMP_ALL_BLOCKS, else the first and the
+    last DUMP_RUN_BLOCKS blocks (the tail block included) and DUMP_RUNS
+    aligned runs drawn from a stream seeded by nblocks alone, so two builds
+    dump the same blocks."""
+    if nblocks <= DUMP_ALL_BLOCKS:
+        return [(0, nblocks)]
+    nruns = nblocks // DUMP_RUN_BLOCKS
+    rng = random.Random(0xD0FF + nblocks)
+    picks = set(rng.sample(range(1, nruns - 1), DUMP_RUNS))
+    runs = [(0, DUMP_RUN_BLOCKS)] + [(r * DUMP_RUN_BLOCKS, (r + 1) * DUMP_RUN_BLOCKS) for r in sorted(picks)]
+    return runs + [(nblocks - DUMP_RUN_BLOCKS, nblocks)]
+
+
+def words_f64(raw):
+    """Big-endian bytes as their 32-bit words in float64 (exact)."""
+    import numpy as np
+    return np.frombuffer(raw, dtype=">u4").astype(np.float64)
+
+
+def dump_encode(out_dir, R, ctx, L, tptr, nblocks, w, tries):
+    """--dump-outputs of an encode: what hb_encode's caller receives from the
+    last timed step -- this rank's tags (one row of w / 4 big-endian 32-bit
+    words per dumped block, dump_runs) and that step's PRF try count;
+    `tag_blocks` names the dumped blocks."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if R.world == 1 else "_rank%d" % R.rank
+    rows, blocks = [], []
+    for r0, r1 in dump_runs(nblocks):
+        raw = np.empty((r1 - r0) * w, dtype=np.uint8)
+        ctx.check(L.hb_memcpy(ctx.h, raw.ctypes.data, tptr.value + r0 * w, raw.nbytes, 2))
+        rows.append(words_f64(raw).reshape(r1 - r0, w // 4))
+        blocks.append(np.arange(r0, r1, dtype=np.float64))
+    np.save(os.path.join(out_dir, "tags%s.npy" % sfx), np.concatenate(rows))
+    np.save(os.path.join(out_dir, "tag_blocks%s.npy" % sfx), np.concatenate(blocks))
+    np.save(os.path.join(out_dir, "tries%s.npy" % sfx), np.array([tries], dtype=np.float64))
 
 
 def seeded_prime(bits):
@@ -1233,13 +1294,19 @@ def bench_prove(args, cfg, R):
 
     for _ in range(max(1, args.warmup)):
         step()
-    steps = max(args.steps, 20)
+    steps = args.steps
     R.barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         step()
     R.barrier()
     ms = R.reduce((time.perf_counter() - t0) / steps * 1e3, "max")
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        sfx = "" if R.world == 1 else "_rank%d" % R.rank
+        np.save(os.path.join(args.dump_outputs, "mu%s.npy" % sfx), words_f64(mu.raw).reshape(S, w // 4))
+        np.save(os.path.join(args.dump_outputs, "sigma%s.npy" % sfx), words_f64(sg.raw))
     line = {
         "metric": "Swizzle prove() latency, ms per proof (device-resident file and tags)",
         "value": round(ms, 4), "unit": "ms", "n_gpus": R.world,
@@ -1253,9 +1320,9 @@ def bench_prove(args, cfg, R):
         "gathered_bytes_per_proof": chunks * (C + w),
         "build": _native.build_info(),
     }
-    if not cxx:
+    if args.full and not cxx:
         line["verify"] = verify_timing(ctx, L, pb, S, fk, ak, nblocks, ck, chunks, mu, sg, max(2, steps // 4))
-    if R.rank == 0 and not args.no_cpu_baseline and not cxx:
+    if args.full and R.rank == 0 and not args.no_cpu_baseline and not cxx:
         import numpy as np
         from oracle import oracle as O
         host = np.empty(length, dtype=np.uint8)
