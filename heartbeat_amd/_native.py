@@ -78,6 +78,9 @@ SIGNATURES = [
     ("hb_ctx_wait", _c.c_int, [_P, _c.POINTER(_c.c_uint64)]),
     ("hb_ctx_prepare", _c.c_int, [_P, _c.c_uint32]),
     ("hb_ctx_num_cus", _c.c_int, [_P, _c.POINTER(_c.c_int)]),
+    ("hb_ctx_set_digest_cache", _c.c_int, [_P, _c.c_uint64]),
+    ("hb_ctx_digest_cache_info", _c.c_int, [_P, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                            _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
     ("hb_last_kernel_phases", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.c_uint32]),
     ("hb_merkle_offsets", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint64, _c.c_uint64, _c.c_uint64, _P]),
     ("hb_merkle_chunk_hmacs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint64, _P, _c.c_uint64, _P,
@@ -201,6 +204,25 @@ class Context(object):
         n = ctypes.c_int()
         self.check(lib().hb_ctx_num_cus(self.h, ctypes.byref(n)))
         return n.value
+
+    def set_digest_cache(self, max_bytes):
+        """Cap of the context's table of per-index SHA-256 digests in bytes
+        (hb_ctx_set_digest_cache; 32 bytes per block of the largest index
+        range encoded, default 8 GiB); 0 frees the table and turns it off."""
+        with self.lock:
+            self.check(lib().hb_ctx_set_digest_cache(self.h, int(max_bytes)))
+
+    def digest_cache_info(self):
+        """State of the digest table (hb_ctx_digest_cache_info): the valid
+        index range [lo, hi), the bytes allocated, and what the last encode
+        did with it ("none": hashed, "store": hashed and stored, "load")."""
+        lo, hi, nbytes = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        mode = ctypes.c_uint32()
+        with self.lock:
+            self.check(lib().hb_ctx_digest_cache_info(self.h, ctypes.byref(lo), ctypes.byref(hi),
+                                                      ctypes.byref(nbytes), ctypes.byref(mode)))
+        return {"lo": lo.value, "hi": hi.value, "bytes": nbytes.value,
+                "last_mode": ("none", "store", "load")[mode.value]}
 
     def last_kernel_ms(self):
         ms = ctypes.c_double()

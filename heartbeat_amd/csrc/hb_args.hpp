@@ -3,6 +3,7 @@
 // round keys, modulus and range are wave-uniform scalar operands.
 #pragma once
 #include "hb_lane.hpp"
+#include "hb_digest_cache.hpp"
 
 // Set by hb_ctx_prepare on its thread: the launchers only load code objects
 // (hb_kernels.hpp, HB_LAUNCH).  Defined in hb_kern_misc.hip.
@@ -34,7 +35,9 @@ extern thread_local bool hb_load_only;
 // first output word (all but ~2^-32 of them) are listed before the try with
 // the SHA-256 digest of their index (flags bit 0), which the retry pass then
 // reads instead of recomputing it: 1,092.3 vs 1,088.4 GiB/s with
-// HB_RETRY_DIGEST=0
+// HB_RETRY_DIGEST=0.  With the context's digest table
+// (EncodeArgs::dig_mode store or load) nothing is listed early and `dig` is
+// neither written nor read: the retry pass reads the table by `blk`.
 #ifndef HB_RETRY_DIGEST
 #define HB_RETRY_DIGEST 1
 #endif
@@ -106,6 +109,14 @@ struct EncodeArgs {
     // jobs per queue refill in the first / retry passes and the single-pass
     // engine (0: HB_QUEUE_CHUNK; hb_runtime.cpp encode_qchunk)
     u64 qchunk;
+    // the context's digest table (hb_digest_cache.hpp; two-pass encode):
+    // entry k = the 8 big-endian words of SHA256(str(dig_lo + k)).  dig_mode
+    // HB_DIG_LOAD: both passes read the digest of block_base + job there;
+    // HB_DIG_STORE: the first pass hashes and stores it, the retry pass reads
+    // it; HB_DIG_NONE: both hash
+    u32 *dig_tab;
+    u64 dig_lo;
+    u32 dig_mode;
 };
 
 // The split wide-prime encode's argument blocks: hb_wide_args.hpp.

@@ -999,6 +999,42 @@ __device__ __forceinline__ void hb_finish_T(u32 T[2 * NL + 1], const u32 F[NL], 
 }
 #endif
 
+// The digest table (hb_digest_cache.hpp): entry of block `blk` of the launch.
+template <int NL>
+__device__ __forceinline__ uint4 *hb_dig_entry(const EncodeArgs<NL> &A, u64 blk) {
+    return reinterpret_cast<uint4 *>(A.dig_tab + (A.block_base + blk - A.dig_lo) * 8);
+}
+
+template <int NL>
+__device__ __forceinline__ void hb_dig_load(const EncodeArgs<NL> &A, u64 blk, u32 dig[8]) {
+    const uint4 *e = hb_dig_entry<NL>(A, blk);
+    const uint4 a = e[0], b = e[1];
+    dig[0] = a.x; dig[1] = a.y; dig[2] = a.z; dig[3] = a.w;
+    dig[4] = b.x; dig[5] = b.y; dig[6] = b.z; dig[7] = b.w;
+}
+
+// SHA256(str(block_base + job)) of a first try (wave-uniform call).
+// DLOAD (HB_DIG_LOAD, hb_encode_first_load_kernel): two 16-byte loads per
+// lane, 2 KiB contiguous per wave (HbPool deals next + rank); an idle lane
+// (job 0) reads block 0's entry, which exists whenever a lane of the launch
+// is active.  Otherwise hash, and with HB_DIG_STORE (a kernel argument: a
+// scalar branch) the active lanes store.  The load is a kernel of its own:
+// with both the load and the hash + store behind one run-time mode the
+// 256-bit first pass took 48 bytes of scratch per lane (either alone: none).
+template <int NL, bool DLOAD>
+__device__ __forceinline__ void hb_first_digest(const EncodeArgs<NL> &A, u64 job, bool act, u32 dig[8]) {
+    if constexpr (DLOAD) {
+        hb_dig_load<NL>(A, job, dig);
+        return;
+    }
+    hb_sha256_decimal(A.block_base + job, dig);
+    if (A.dig_mode == HB_DIG_STORE && act) {
+        uint4 *e = hb_dig_entry<NL>(A, job);
+        e[0] = make_uint4(dig[0], dig[1], dig[2], dig[3]);
+        e[1] = make_uint4(dig[4], dig[5], dig[6], dig[7]);
+    }
+}
+
 // End of the first try of every lane's block (wave-uniform call): accepted
 // blocks are tagged, rejected ones go to the retry list with their shift
 // register (and, with the MFMA MAC, with sum_j alpha_j m_j mod p, so that the
@@ -1055,7 +1091,8 @@ __device__ __forceinline__ void hb_first_finish(const EncodeArgs<NL> &A, const L
             if (slot < A.retry_cap) {
                 listed = true;
                 e = A.retry + slot;
-                // no digest stored (flags 0): the retry pass hashes the index
+                // no digest stored (flags 0): the retry pass hashes the index,
+                // or with a digest table (A.dig_mode) reads the block's entry
                 *reinterpret_cast<uint4 *>(e) = make_uint4((u32)job, (u32)(job >> 32), 0u, 0u);
             }
         }
@@ -1109,8 +1146,8 @@ __device__ __forceinline__ void hb_first_finish(const EncodeArgs<NL> &A, const L
     if (done) h.accept(job, out);
 }
 
-template <int NL, int NR, int ALIGN>
-__global__ __launch_bounds__((HbEncWg<NL, ALIGN>::v), HbEncodeOcc<NL>::v) void hb_encode_first_kernel(EncodeArgs<NL> A) {
+template <int NL, int NR, int ALIGN, bool DLOAD>
+__device__ __forceinline__ void hb_encode_first_body(const EncodeArgs<NL> &A) {
     // MFMA MAC for 256-bit primes with aligned full-width sectors (A.mfma set by the host)
     constexpr bool MF = NL == 8 && ALIGN == 16;
     // MF: the T-table image plus the MFMA A fragments (HB_MFMA_NT x S x 1 KiB,
@@ -1157,7 +1194,7 @@ __global__ __launch_bounds__((HbEncWg<NL, ALIGN>::v), HbEncodeOcc<NL>::v) void h
         u64 pre_base = 0, pre_mask = 0;
         {
             u32 dig[8];
-            hb_sha256_decimal(A.block_base + job, dig);
+            hb_first_digest<NL, DLOAD>(A, job, act, dig);
             hb_prf_prefix<NL>(A.pfx, A.o0, A.prf, dig[0], sr, out);
 #if HB_RETRY_DIGEST
             // the first output word alone decides all but ~2^-32 of the
@@ -1183,6 +1220,18 @@ __global__ __launch_bounds__((HbEncWg<NL, ALIGN>::v), HbEncodeOcc<NL>::v) void h
     if (hb_lane_id() == 0 && failed) atomicAdd(A.queue + 2, (unsigned long long)failed);
 }
 
+// the first pass hashing the indices (and storing the digests with
+// HB_DIG_STORE) / reading their digests from the table (HB_DIG_LOAD)
+template <int NL, int NR, int ALIGN>
+__global__ __launch_bounds__((HbEncWg<NL, ALIGN>::v), HbEncodeOcc<NL>::v) void hb_encode_first_kernel(EncodeArgs<NL> A) {
+    hb_encode_first_body<NL, NR, ALIGN, false>(A);
+}
+
+template <int NL, int NR, int ALIGN>
+__global__ __launch_bounds__((HbEncWg<NL, ALIGN>::v), HbEncodeOcc<NL>::v) void hb_encode_first_load_kernel(EncodeArgs<NL> A) {
+    hb_encode_first_body<NL, NR, ALIGN, true>(A);
+}
+
 template <int NL, int ALIGN>
 struct RetryHandler {
     static constexpr u32 kResumedTries = 1;   // the first pass ran one try
@@ -1192,17 +1241,25 @@ struct RetryHandler {
         const uint4 v = *reinterpret_cast<const uint4 *>(A.retry[job].sr);
         sr[0] = v.x; sr[1] = v.y; sr[2] = v.z; sr[3] = v.w;
     }
-#if HB_RETRY_DIGEST
-    // the digest the first pass stored (flags bit 0), else hash the index
+    // the block's entry of the digest table (the first pass stored or read
+    // it, and has finished: stream order), else the digest the first pass
+    // listed (flags bit 0), else hash the index
     __device__ __forceinline__ bool digest(u64 job, u32 dig[8]) const {
         const HbRetry &r = A.retry[job];
+        if (A.dig_mode != HB_DIG_NONE) {
+            hb_dig_load<NL>(A, r.blk, dig);
+            return true;
+        }
+#if HB_RETRY_DIGEST
         if (!(r.flags & 1u)) return false;
         const uint4 a = *reinterpret_cast<const uint4 *>(r.dig), b = *reinterpret_cast<const uint4 *>(r.dig + 4);
         dig[0] = a.x; dig[1] = a.y; dig[2] = a.z; dig[3] = a.w;
         dig[4] = b.x; dig[5] = b.y; dig[6] = b.z; dig[7] = b.w;
         return true;
-    }
+#else
+        return false;
 #endif
+    }
     __device__ __forceinline__ void accept(u64 job, const u32 F[NL]) const {
         const u64 blk = A.retry[job].blk;
         if constexpr (ALIGN == 0) {   // split wide-prime encode: F for hb_wmac_kernel
@@ -2157,7 +2214,10 @@ hipError_t hb_launch_encode_pass(const EncodeArgs<NL> &A, int nr, int align, int
         if (align == 0) return hipErrorInvalidValue;               \
         HB_ENC_AL(K);                                              \
     } while (0)
-    if constexpr (PASS == 1) HB_ENC_AL0(hb_encode_first_kernel);
+    if constexpr (PASS == 1) {
+        if (A.dig_mode == HB_DIG_LOAD) HB_ENC_AL0(hb_encode_first_load_kernel);
+        else HB_ENC_AL0(hb_encode_first_kernel);
+    }
     else if constexpr (PASS == 2) HB_ENC_AL0(hb_encode_retry_kernel);
     else if constexpr (PASS == 3) HB_ENC_AL0(hb_cxx_encode_kernel);
     else HB_ENC_AL(hb_encode_kernel);

@@ -107,6 +107,16 @@ struct hb_ctx {
     DevBuf alpha_raw, alpha_mont, xs, vals, vals2, wts, idx, partials, sums, data[2], tags, blen, gtags;
     DevBuf pfx, retry;   // two-pass encode: CFB prefix image, retry list
     DevBuf afrag;        // MFMA MAC: digit fragments of alpha_j R mod p
+    // digest table of the two-pass encode (hb_digest_cache.hpp): entry k of
+    // `dig` is SHA256(str(dig_alloc.lo + k)); dig_valid (inside dig_alloc) is
+    // what completed store-mode encodes have written; dig_next is the valid
+    // range a store-mode encode in progress leaves once it has completed
+    // without error (dig_commit).  Only touched on `stream`.
+    DevBuf dig;
+    HbDigRange dig_alloc = {0, 0}, dig_valid = {0, 0}, dig_next = {0, 0};
+    bool dig_next_set = false;
+    u64 dig_cap = 8192ull << 20;
+    u32 dig_last_mode = HB_DIG_NONE;
     DevBuf ctl;          // wsum column counters + flags (zero between operations)
     DevBuf mseeds, moffs, mdig;   // Merkle chunk seeds, offsets, HMAC digests
     DevBuf gdev;         // device-resident prove: the challenged blocks and tags, gathered
@@ -219,6 +229,7 @@ const SwitchName kSwitches[] = {
     {"HB_WMAC_WPE", HB_SW_WMAC_WPE},
     {"HB_WIDE_SYNC_ALPHA", HB_SW_WIDE_SYNC_ALPHA},
     {"HB_QCHUNK", HB_SW_QCHUNK},
+    {"HB_DIGEST_CACHE_MIB", HB_SW_DIGEST_CACHE},
 };
 
 int nl_for_bits(int bits) {
@@ -424,8 +435,14 @@ void prepare_nl(hb_ctx *c) {
     memset(&E, 0, sizeof E);
     for (int pass = 0; pass <= 3; ++pass)
         for (int align : {16, 1}) (void)hb_launch_encode<NL>(E, 14, align, pass, 0, c->stream);
+    // the first pass reading the digest table is a kernel of its own
+    // (hb_encode_first_load_kernel), the steady state of repeated encodes
+    EncodeArgs<NL> EL = E;
+    EL.dig_mode = HB_DIG_LOAD;
+    for (int align : {16, 1}) (void)hb_launch_encode<NL>(EL, 14, align, 1, 0, c->stream);
     if constexpr (NL >= 16) {   // the split wide-prime encode (wide_plan)
         for (int pass = 1; pass <= 3; ++pass) (void)hb_launch_encode<NL>(E, 14, 0, pass, 0, c->stream);
+        (void)hb_launch_encode<NL>(EL, 14, 0, 1, 0, c->stream);
         WtabArgs<NL> WT;
         memset(&WT, 0, sizeof WT);
         (void)hb_launch_wtab<NL>(WT, c->stream);
@@ -898,6 +915,74 @@ struct HostWindows {
     }
 };
 
+// ------------------------------------------------------------------ digest table
+void dig_free(hb_ctx *c) {
+    c->dig.release();
+    c->dig_alloc = c->dig_valid = c->dig_next = HbDigRange{0, 0};
+    c->dig_next_set = false;
+}
+
+// A store-mode encode has completed without error: its range is valid.
+void dig_commit(hb_ctx *c) {
+    if (c->dig_next_set) c->dig_valid = c->dig_next;
+    c->dig_next_set = false;
+}
+
+// The table's part in one hb_encode of blocks [base, base + n): the policy's
+// mode (hb_digest_plan), with the table allocated, and the valid entries it
+// keeps moved, for a store.  Nothing here fails the encode: a table that
+// cannot be had only means HB_DIG_NONE.  The stream is idle of table users
+// (every entry point settles an async encode first).
+// Two costs of the single-buffer design:
+//  - growing a kept range holds the old and the new table until the copy is
+//    done, so device memory can for that moment reach nearly twice the cap
+//    (a failing hipMalloc of the new table only means HB_DIG_NONE, the old
+//    one stays);
+//  - a table of the request alone reuses (or replaces) the buffer, so the old
+//    valid range is given up BEFORE the encode runs: an encode that then
+//    fails leaves an empty valid range, not the earlier one.  An encode that
+//    fails in load mode, or in a store that keeps the old entries, leaves the
+//    valid range as it was.
+// The encode's own buffers (tags, host staging) are allocated before this is
+// called, so the table never takes memory an encode needs to run at all.
+u32 dig_prepare(hb_ctx *c, u64 base, u64 n) {
+    u64 cap = c->dig_cap;
+    if (const char *v = sw_env(c, "HB_DIGEST_CACHE_MIB")) cap = strtoull(v, nullptr, 10) << 20;
+    c->dig_next_set = false;
+    const HbDigPlan P = hb_digest_plan(c->dig_valid, base, n, cap);
+    if (P.mode != HB_DIG_STORE) return P.mode;
+    const size_t bytes = (size_t)(P.alloc.hi - P.alloc.lo) * HB_DIG_ENTRY;
+    if (!P.keep) {
+        // a table of the request alone: the old entries go
+        c->dig_valid = HbDigRange{0, 0};
+        if (c->dig.ensure(bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            dig_free(c);
+            return HB_DIG_NONE;
+        }
+    } else if (P.alloc.lo != c->dig_alloc.lo || P.alloc.hi != c->dig_alloc.hi) {
+        DevBuf nb;
+        const size_t keep = (size_t)(c->dig_valid.hi - c->dig_valid.lo) * HB_DIG_ENTRY;
+        hipError_t e = nb.ensure(bytes);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((uint8_t *)nb.p + (size_t)(c->dig_valid.lo - P.alloc.lo) * HB_DIG_ENTRY,
+                               (const uint8_t *)c->dig.p + (size_t)(c->dig_valid.lo - c->dig_alloc.lo) * HB_DIG_ENTRY,
+                               keep, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // the old table is freed below
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            nb.release();
+            return HB_DIG_NONE;
+        }
+        c->dig.release();
+        c->dig = nb;
+    }
+    c->dig_alloc = P.alloc;
+    c->dig_next = P.valid;
+    c->dig_next_set = true;
+    return HB_DIG_STORE;
+}
+
 // Complete an HB_ASYNC encode: wait for its kernels, read its PRF counters;
 // the status is kept for hb_ctx_wait.  Every other entry point settles first
 // (its own kernels would reuse the counters and scratch buffers).
@@ -924,7 +1009,9 @@ void settle(hb_ctx *c) {
     c->last_ms = ms;
     if (q[2] || r[2]) return done(fail(c, HB_EINVAL, "PRF rejection sampling did not terminate for some blocks"));
     c->pend_tries += q[1] + r[1];
-    done(check_prf_slots(c));
+    const int rc = check_prf_slots(c);
+    if (rc == 0) dig_commit(c);
+    done(rc);
 }
 
 // ------------------------------------------------------------------ split wide-prime encode
@@ -1184,6 +1271,25 @@ int encode_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &p
         A.retry = (HbRetry *)c->retry.p;
         A.retry_count = q0 + 3;
         mark("retry list");
+    }
+    // (host data: the staging buffers first, so that the digest table below
+    // cannot take the memory they need)
+    if (!data_dev) {
+        HB_CHECK(c->data[0].ensure((size_t)(cb * C)), "hipMalloc(staging)");
+        HB_CHECK(c->data[1].ensure((size_t)(cb * C)), "hipMalloc(staging)");
+    }
+    // the digest table: one decision for the call's whole index range
+    c->dig_next_set = false;
+    c->dig_last_mode = HB_DIG_NONE;
+    if (two_pass) {
+        A.dig_mode = c->dig_last_mode = dig_prepare(c, block_base, nblocks);
+        A.dig_tab = (u32 *)c->dig.p;
+        A.dig_lo = c->dig_alloc.lo;
+        // with a table the early retry listing has no digest to save: every
+        // rejected first try is listed after the try, and the retry pass
+        // reads the table
+        if (A.dig_mode != HB_DIG_NONE) A.rtop = 0xffffffffu;
+        mark("digest table");
     }
     if (two_pass && !cxx) {
         HB_CHECK(c->pfx.ensure(HB_PFX_BYTES), "hipMalloc(prefix)");
@@ -1491,6 +1597,7 @@ int encode_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &p
     if (tries_out) *tries_out = q[1] + r[1];
     for (int s = 0; s < 16; ++s)
         if (qs[s * HB_QSLOT + 2]) return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate");
+    dig_commit(c);
     return 0;
 }
 
@@ -2255,7 +2362,7 @@ void hb_ctx_destroy(hb_ctx *c) {
     DevBuf *bufs[] = {&c->alpha_raw, &c->alpha_mont, &c->xs, &c->vals, &c->vals2, &c->wts, &c->idx,
                       &c->partials, &c->sums, &c->data[0], &c->data[1], &c->tags, &c->blen, &c->gtags,
                       &c->pfx, &c->retry, &c->ctl, &c->afrag, &c->mseeds, &c->moffs, &c->mdig, &c->gdev,
-                      &c->facc, &c->gup, &c->wpw, &c->wtab};
+                      &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
@@ -2294,6 +2401,31 @@ int hb_last_kernel_phases(hb_ctx *c, double *ms, uint32_t n) {
         ms[k] = f;
     }
     return (int)k;
+}
+
+int hb_ctx_set_digest_cache(hb_ctx *c, uint64_t max_bytes) {
+    if (!c) return HB_EINVAL;
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    settle(c);
+    c->dig_cap = max_bytes;
+    if (c->dig.n > max_bytes || max_bytes < HB_DIG_ENTRY) {
+        HB_CHECK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+        dig_free(c);
+    }
+    return 0;
+}
+
+int hb_ctx_digest_cache_info(hb_ctx *c, uint64_t *lo, uint64_t *hi, uint64_t *bytes, uint32_t *last_mode) {
+    if (!c) return HB_EINVAL;
+    if (c->pending) {
+        HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+        settle(c);
+    }
+    if (lo) *lo = c->dig_valid.lo;
+    if (hi) *hi = c->dig_valid.hi;
+    if (bytes) *bytes = c->dig.n;
+    if (last_mode) *last_mode = c->dig_last_mode;
+    return 0;
 }
 
 int hb_ctx_num_cus(const hb_ctx *c, int *out) {

@@ -127,6 +127,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_WMAC_WPE 1048576u     /* HB_WMAC_WPE=1|3|5: hb_wmac_kernel built for another waves-per-SIMD bound (1: the compiler's choice) */
 #define HB_SW_WIDE_SYNC_ALPHA 2097152u /* HB_WIDE_SYNC_ALPHA: the split encode computes alpha and its digit table on the compute stream, before the PRF passes, instead of beside them */
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
+#define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
 uint32_t hb_test_switches(void);
 
 /* Number of visible HIP devices (multi-GPU sharding of encode / prove opens
@@ -171,6 +172,24 @@ int hb_ctx_wait(hb_ctx *ctx, uint64_t *tries_out);
  * launch: ~5 ms for the 256-bit unit).  Optional; replaces nothing in the
  * reference (setup, like creating a library handle). */
 int hb_ctx_prepare(hb_ctx *ctx, uint32_t prime_bits);
+
+/* The digest table of the two-pass encode.  Every block's PRF input is
+ * SHA256(str(block index)) (heartbeat/util.py:91), which depends on the index
+ * alone -- not on the file, the keys or the prime -- so a context keeps the
+ * digests of one contiguous index range on the device, 32 bytes per block
+ * (1/16 of the file at S = 16 with 32-byte sectors, as large as the file at
+ * S = 1): the first encode of a range stores them while it hashes, later
+ * encodes inside the range load them instead.  The cxx prf, the single-pass
+ * encode and the small / mid-size paths do not use it.
+ * hb_ctx_set_digest_cache: the most bytes the table may take (default 8 GiB:
+ * 2^28 indices); a table larger than that is freed, and 0 turns the feature
+ * off.  A table that does not fit, or cannot be allocated, only means that
+ * the encode hashes.  Replaces nothing in the reference.
+ * hb_ctx_digest_cache_info: the valid index range [*lo, *hi), the bytes
+ * allocated and what the last hb_encode did (0 hashed without the table,
+ * 1 hashed and stored, 2 loaded); any pointer may be NULL. */
+int hb_ctx_set_digest_cache(hb_ctx *ctx, uint64_t max_bytes);
+int hb_ctx_digest_cache_info(hb_ctx *ctx, uint64_t *lo, uint64_t *hi, uint64_t *bytes, uint32_t *last_mode);
 
 /* ceil(bitlen(p)/8): width of every tag / mu / sigma value. */
 size_t hb_width(const uint8_t *p_be, size_t p_len);
