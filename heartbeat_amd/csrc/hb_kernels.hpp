@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "hb_args.hpp"
+#include "hb_mac_src.hpp"
 
 #define HB_LDS_WORDS (HB_TAB_BYTES / 4)
 
@@ -690,7 +691,7 @@ typedef int32_t hb_i32x16 __attribute__((ext_vector_type(16)));
 
 template <int NL>
 __device__ __forceinline__ bool hb_block_full(const EncodeArgs<NL> &A, u64 job) {
-    return (job + 1) * A.C <= A.len;
+    return hb_mac_block_ok(true, job, A.C, A.len);
 }
 
 // Wave-uniform call.  Returns whether THIS lane's T is valid (active lane,
@@ -716,6 +717,13 @@ __device__ __forceinline__ bool hb_block_full(const EncodeArgs<NL> &A, u64 job) 
 #define HB_AES_PRIO 2
 #endif
 
+// What a MAC load returned, or zero for a lane whose address was the fallback
+// (hb_mac_src.hpp).  A select AFTER the load: the loads of a round go out
+// together and the waits between their uses are counted.  (An AND with a
+// lane mask instead made the scheduler interleave load, vmcnt(0), MFMA; a
+// scheduling barrier after the loads cost 36-44 bytes of scratch.)
+__device__ __forceinline__ hb_i32x4 hb_loaded(bool ok, hb_i32x4 v) { return ok ? v : hb_i32x4{0, 0, 0, 0}; }
+
 // x of lane (l ^ 1) / (l ^ 2) within the lane's quad (DPP quad_perm)
 __device__ __forceinline__ int32_t hb_quad_x1(int32_t x) { return __builtin_amdgcn_mov_dpp(x, 0xB1, 0xf, 0xf, false); }
 __device__ __forceinline__ int32_t hb_quad_x2(int32_t x) { return __builtin_amdgcn_mov_dpp(x, 0x4E, 0xf, 0xf, false); }
@@ -731,13 +739,17 @@ __device__ __forceinline__ int32_t hb_quad_x2(int32_t x) { return __builtin_amdg
 // transpose inside each quad (lane bits 0-1 <-> load index, two DPP exchange
 // stages) then leaves in V[r'] at lane (h, n) chunk 4h + r' of block n: the
 // MFMA B layout, with the A fragments of slot j0 + r' built for those chunks
-// (hb_runtime.cpp, mfma_tables).
+// (hb_runtime.cpp, mfma_tables).  The four loads go out together from
+// addresses that are valid for every lane (hb_mac_src.hpp); a lane without a
+// block zeroes what it read.
 __device__ __forceinline__ void hb_line_loads(const unsigned char *const blk[4], const bool okr[4], u32 off,
                                               hb_i32x4 V[4]) {
     hb_i32x4 L[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        L[r] = okr[r] ? *reinterpret_cast<const hb_i32x4 *>(blk[r] + off) : hb_i32x4{0, 0, 0, 0};
+        L[r] = *reinterpret_cast<const hb_i32x4 *>(blk[r] + off);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) L[r] = hb_loaded(okr[r], L[r]);
     const u32 i = hb_lane_id() & 3u;
     const bool b0 = i & 1u, b1 = i & 2u;
     hb_i32x4 M[4];
@@ -767,9 +779,11 @@ template <int NL, bool ALDS>
 __device__ __forceinline__ bool hb_mfma_block_acc(const EncodeArgs<NL> &A, const hb_i32x4 *afl, u64 job, bool active,
                                                   u32 T[2 * NL + 1]) {
     static_assert(NL == 8, "MFMA MAC: 256-bit primes only");
-    const u32 l = hb_lane_id(), h = l >> 5, n = l & 31u;
+    const u32 l = hb_lane_id();
     const bool mine = active && hb_block_full(A, job);
     const u32 S = A.S;
+    // where a lane without a block loads from (hb_mac_src.hpp)
+    const unsigned char *fb = reinterpret_cast<const unsigned char *>(A.afrag);
     constexpr int NK = 4 * HB_MFMA_NT;   // limbs per lane half and group
     long long G[2][NK];   // G[g][k]: limb 2k + h of group g's column-n block
 #pragma unroll
@@ -785,10 +799,10 @@ __device__ __forceinline__ bool hb_mfma_block_acc(const EncodeArgs<NL> &A, const
             bool okr[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int src = (int)(32 * g + (n & ~3u) + r);
+                const int src = (int)hb_mac_line_src_lane(l, g, (u32)r);
                 const u64 jb = (u64)__shfl((long long)job, src);
                 okr[r] = __shfl((int)mine, src) != 0;
-                blk[r] = A.data + jb * A.C + 64u * h + 16u * (l & 3u);
+                blk[r] = hb_mac_src(okr[r], A.data, jb, A.C, fb, hb_mac_line_lane_off(l));
             }
             for (u32 j0 = 0; j0 < S; j0 += 4) {
                 hb_i32x4 V[4];
@@ -806,9 +820,11 @@ __device__ __forceinline__ bool hb_mfma_block_acc(const EncodeArgs<NL> &A, const
 #endif
         {
         // the block of column n in group g: lane 32 g + n's
-        const u64 jb = (u64)__shfl((long long)job, (int)(32 * g + n));
-        const bool ok = __shfl((int)mine, (int)(32 * g + n)) != 0;
-        const hb_i32x4 *src = reinterpret_cast<const hb_i32x4 *>(A.data + jb * A.C + 16u * h);
+        const int sl = (int)hb_mac_sector_src_lane(l, g);
+        const u64 jb = (u64)__shfl((long long)job, sl);
+        const bool ok = __shfl((int)mine, sl) != 0;
+        const hb_i32x4 *src =
+            reinterpret_cast<const hb_i32x4 *>(hb_mac_src(ok, A.data, jb, A.C, fb, hb_mac_sector_lane_off(l)));
         for (u32 j0 = 0; j0 < S; j0 += HB_MFMA_BATCH) {
             hb_i32x4 b[HB_MFMA_BATCH];
 #pragma unroll
@@ -817,8 +833,11 @@ __device__ __forceinline__ bool hb_mfma_block_acc(const EncodeArgs<NL> &A, const
                 (void)ok; (void)src;
                 b[jj] = hb_i32x4{(int32_t)jb, (int32_t)(j0 + jj), 1, 2};
 #else
-                b[jj] = ok && j0 + jj < S ? src[2 * (j0 + jj)] : hb_i32x4{0, 0, 0, 0};
+                // (past the last sector: sector S - 1 again, unused below)
+                b[jj] = src[2 * (j0 + jj < S ? j0 + jj : S - 1)];
 #endif
+#pragma unroll
+            for (int jj = 0; jj < HB_MFMA_BATCH; ++jj) b[jj] = hb_loaded(ok, b[jj]);
 #pragma unroll
             for (int jj = 0; jj < HB_MFMA_BATCH; ++jj) {
                 // past the last sector: a zero B (after the -128 shift) against
@@ -883,17 +902,19 @@ template <int NL, bool ALDS>
 __device__ __forceinline__ bool hb_mfma16_block_acc(const EncodeArgs<NL> &A, const hb_i32x4 *afl, u64 job,
                                                     bool active, u32 T[2 * NL + 1]) {
     static_assert(NL == 8, "MFMA MAC: 256-bit primes only");
-    const u32 l = hb_lane_id(), q = l >> 4, n = l & 15u;
+    const u32 l = hb_lane_id();
     const bool mine = active && hb_block_full(A, job);
     const u32 np = A.S / 2;   // K slices of 64 bytes (2 sectors)
     const unsigned char *blk[4];
     bool okg[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const int src = (int)(16 * g + n);
+        const int src = (int)hb_mac16_src_lane(l, (u32)g);
         const u64 jb = (u64)__shfl((long long)job, src);
         okg[g] = __shfl((int)mine, src) != 0;
-        blk[g] = A.data + jb * A.C + 16u * q;
+        // a lane without a block reads the A fragments instead (hb_mac_src.hpp)
+        blk[g] = hb_mac_src(okg[g], A.data, jb, A.C, reinterpret_cast<const unsigned char *>(A.afrag),
+                            hb_mac16_lane_off(l));
     }
     hb_i32x4 acc[4][2];
 #pragma unroll
@@ -902,7 +923,8 @@ __device__ __forceinline__ bool hb_mfma16_block_acc(const EncodeArgs<NL> &A, con
         const hb_i32x4 a0 = afl[(2 * p) * 64 + l], a1 = afl[(2 * p + 1) * 64 + l];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const hb_i32x4 bb = b[g] ^ (int32_t)0x80808080;
+            // loaded by every lane; zero where the lane's column has no block
+            const hb_i32x4 bb = hb_loaded(okg[g], b[g]) ^ (int32_t)0x80808080;
             acc[g][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, bb, acc[g][0], 0, 0, 0);
             acc[g][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, bb, acc[g][1], 0, 0, 0);
         }
@@ -913,8 +935,8 @@ __device__ __forceinline__ bool hb_mfma16_block_acc(const EncodeArgs<NL> &A, con
         hb_i32x4 b0[4], b1[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            b0[g] = okg[g] ? *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * p) : hb_i32x4{0, 0, 0, 0};
-            b1[g] = okg[g] ? *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * (p + 1)) : hb_i32x4{0, 0, 0, 0};
+            b0[g] = *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * p);
+            b1[g] = *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * (p + 1));
         }
         slice(b0, p);
         slice(b1, p + 1);
@@ -923,7 +945,7 @@ __device__ __forceinline__ bool hb_mfma16_block_acc(const EncodeArgs<NL> &A, con
         hb_i32x4 b0[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-            b0[g] = okg[g] ? *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * p) : hb_i32x4{0, 0, 0, 0};
+            b0[g] = *reinterpret_cast<const hb_i32x4 *>(blk[g] + 64u * p);
         slice(b0, p);
     }
     // X[g][d]: dwords of limbs q (d = 0, 1) and 4 + q (d = 2, 3) of block 16 g + n
