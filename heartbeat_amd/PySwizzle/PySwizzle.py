@@ -10,6 +10,7 @@ Same class names, constructor arguments, method signatures, defaults,
     Proof() .mu .sigma                            PySwizzle.py:198-224
     PySwizzle(sectors=10, key=None, prime=None, primebits=1024)
         encode(file) -> (Tag, State)              PySwizzle.py:279-314
+        encode_many(files) -> [(Tag, State)]      a loop over :279-311, one GPU call
         gen_challenge(state) -> Challenge         PySwizzle.py:316-331
         prove(file, chal, tag) -> Proof           PySwizzle.py:333-370
         verify(proof, chal, state) -> bool        PySwizzle.py:372-395
@@ -284,6 +285,23 @@ class PySwizzle(object):
         state.encrypt(self.key)
         return (tag, state)
 
+    def encode_many(self, files):
+        """Tag every file of `files` in one batched GPU call
+        (hb_encode_many): [(Tag, State), ...], each file with fresh random
+        keys, exactly as a loop of encode() (PySwizzle.py:279-311) -- which
+        pays every file's longest PRF rejection chain in turn."""
+        self._check()
+        files = list(files)
+        p = int(self.prime)
+        states = [State(_random_bytes(32), _random_bytes(32)) for _ in files]
+        res = encode_files(p, int(self.sectors), [(s.f_key, s.alpha_key) for s in states], files)
+        out = []
+        for state, (tag, nblocks) in zip(states, res):
+            state.chunks = nblocks
+            state.encrypt(self.key)
+            out.append((tag, state))
+        return out
+
     def gen_challenge(self, state):
         """Challenge every block once on average (chunks = #blocks, v_max = p)."""
         state.decrypt(self.key)
@@ -405,6 +423,58 @@ def encode_file(p, sectors, f_key, alpha_key, file, devices=None, register=None)
     finally:
         fb.close()
     return Tag._from_raw(memoryview(out), w), nblocks
+
+
+def encode_files(p, sectors, keys, files):
+    """Batched GPU encode (hb_encode_many) of many file objects / buffers,
+    file i under keys[i] = (f_key, alpha_key): [(Tag, number of blocks), ...].
+    Each file is read from its current position to EOF and left there, as by
+    encode_file; all keys of a batch have one length.  Runs on
+    multi.primary_context() (a batch is not spread over several GPUs)."""
+    p = int(p)
+    files = list(files)
+    keys = list(keys)
+    if len(keys) != len(files):
+        raise HeartbeatError("%d key pairs for %d files" % (len(keys), len(files)))
+    ss = p.bit_length() // 8
+    if ss < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if int(sectors) < 1:
+        raise HeartbeatError("sectors must be positive")
+    kb = [(_kb(fk), _kb(ak)) for fk, ak in keys]
+    if len({len(k) for pair in kb for k in pair}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if not files:
+        return []
+    w = _native.width_of(p)
+    C = ss * int(sectors)
+    fbs, outs = [], []
+    try:
+        descs = (_native.FileDesc * len(files))()
+        for i, file in enumerate(files):
+            fb = FileBuffer(file)
+            fbs.append(fb)
+            nblocks = fb.len // C + 1
+            # the tags land in the array the Tag keeps
+            out = np.empty(nblocks * w, dtype=np.uint8)
+            outs.append((out, nblocks))
+            d = descs[i]
+            d.f_key, d.alpha_key = kb[i]
+            d.data = fb.addr
+            d.len = fb.len
+            d.tags = out.ctypes.data
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        tries = ctypes.c_uint64()
+        with ctx.lock:
+            ctx.check(_native.lib().hb_encode_many(ctx.h, pb, len(pb), int(sectors), len(kb[0][0]), descs,
+                                                   len(files), 0, ctypes.byref(tries)))
+        for fb in fbs:
+            fb.consume()
+    finally:
+        for fb in fbs:
+            fb.close()
+    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
 
 
 # The reference's module path (heartbeat/PySwizzle/PySwizzle.py): pickles of

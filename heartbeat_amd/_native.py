@@ -34,6 +34,14 @@ _ctxs = {}
 _c = ctypes
 _P = _c.c_void_p
 _B = _c.c_char_p
+
+
+class FileDesc(ctypes.Structure):
+    """hb_file_desc (hbswizzle.h): one file of an hb_encode_many batch."""
+    _fields_ = [("f_key", ctypes.c_char_p), ("alpha_key", ctypes.c_char_p), ("data", ctypes.c_void_p),
+                ("len", ctypes.c_uint64), ("tags", ctypes.c_void_p)]
+
+
 SIGNATURES = [
     ("hb_abi_version", _c.c_int, []),
     ("hb_build_flags", _c.c_int, []),
@@ -51,6 +59,8 @@ SIGNATURES = [
     ("hb_encode", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t, _c.c_uint64,
                              _P, _c.c_uint64, _c.c_uint64, _P, _c.c_uint32,
                              _c.POINTER(_c.c_uint64)]),
+    ("hb_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
+                                  _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_block_count", _c.c_uint64, [_B, _c.c_size_t, _c.c_uint32, _c.c_uint64]),
     ("hb_prove", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _c.c_size_t, _c.c_uint64, _B,
                             _c.c_size_t, _P, _c.c_uint64, _P, _c.c_uint64, _c.c_uint32, _P, _P]),

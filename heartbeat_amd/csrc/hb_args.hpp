@@ -313,3 +313,58 @@ struct MerkleArgs {
     unsigned int *flags;          // bit 1: a PRF did not terminate
     const u32 *t0;
 };
+
+// ------------------------------------------------------------------ batched encode
+// hb_encode_many (hb_kern_batch.hip): many small files, each with its own
+// f_key and alpha_key, in one PRF launch and one MAC launch.  The per-file
+// state lives in device tables indexed by a wave-uniform file number; only
+// what the whole batch shares (prime, sector shape) is in the kernel arguments.
+struct BatchFile {
+    const unsigned char *data;    // the file's bytes (device), len of them
+    u64 len;
+    unsigned char *tags;          // nblocks * tw big-endian bytes (device)
+    u64 fbase;                    // the file's first block in the batch's F buffer
+    u32 nblocks;
+    u32 flags;                    // HB_BF_*
+};
+#define HB_BF_LOAD16 1u           // data base, ss and C allow the 16-byte sector loads
+#define HB_BF_TAGS4 2u            // tags 4-byte aligned: dword tag stores
+
+// One quad-engine wave's work: up to 16 PRF evaluations [first, first + count)
+// of one file under one key -- F(k) of its blocks (kind 0) or alpha_j of its
+// sectors (kind 1).
+struct BatchWaveJob {
+    u32 file, kind, first, count;
+};
+
+template <int NL>
+struct BatchPrfArgs {
+    const PrfParams<NL> *prf;     // [2 file + kind]: KeyedPRF(f_key, p), KeyedPRF(alpha_key, p)
+    const BatchFile *files;
+    const BatchWaveJob *jobs;
+    u64 njobs;
+    ModP<NL> mod;
+    u32 r2[NL];                   // R^2 mod p
+    u32 *fv;                      // F(k) of file f at (fbase + k) * NL, little-endian limbs
+    u32 *amont;                   // alpha_j R mod p of file f at (f * S + j) * NL
+    u32 S;
+    const u32 *t0;
+    unsigned long long *queue;    // slot 0: [0] next wave-job, [1] F tries, [2] abandoned F;
+                                  // slot 1 (queue + HB_QSLOT): alpha's tries and abandoned jobs
+};
+
+// A MAC workgroup's blocks: [first, first + blocks per workgroup) of one file.
+struct BatchMacWg {
+    u32 file, first;
+};
+
+template <int NL>
+struct BatchMacArgs {
+    ModP<NL> mod;
+    const BatchFile *files;
+    const BatchMacWg *wgs;        // one entry per workgroup
+    const u32 *fv;
+    const u32 *amont;
+    u64 C;
+    u32 ss, S, tw;
+};

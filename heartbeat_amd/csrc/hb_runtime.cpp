@@ -46,6 +46,10 @@ hipError_t hb_launch_merkle_offsets(const MerkleArgs &, int, hipStream_t);
 hipError_t hb_launch_hmac(const MerkleArgs &, hipStream_t);
 template <int NL> hipError_t hb_launch_wtab(const WtabArgs<NL> &, hipStream_t);
 template <int NL> hipError_t hb_launch_wmac(const WmacArgs<NL> &, hipStream_t);
+// (hb_batch.hpp)
+template <int NL> hipError_t hb_launch_batch_prf(const BatchPrfArgs<NL> &, int, int, hipStream_t);
+template <int NL> u32 hb_batch_mac_bpw(u32);
+template <int NL> hipError_t hb_launch_batch_mac(const BatchMacArgs<NL> &, u32, hipStream_t);
 
 namespace {
 
@@ -126,6 +130,8 @@ struct hb_ctx {
     DevBuf wtab;         // its digit table (A fragments), kz, status word
     Limbs wide_key;      // p of wpw, then ss (wide_prep)
     HostBuf gstage[2];   // host-file prove: pinned gather buffers (blocks | tags), double-buffered
+    DevBuf bdev;         // hb_encode_many: tables | host files | F | alpha | tags of one group of files
+    HostBuf bhost;       // its pinned staging: tables | host files, and the tags coming back
     HostBuf hscratch;    // pinned staging of the encode's small host round trips (alpha, MFMA tables)
     // the alpha D2H into hscratch done / the MFMA-table H2D out of it done
     // (not yet waited for: the next round trip must wait before reusing hscratch)
@@ -230,6 +236,7 @@ const SwitchName kSwitches[] = {
     {"HB_WIDE_SYNC_ALPHA", HB_SW_WIDE_SYNC_ALPHA},
     {"HB_QCHUNK", HB_SW_QCHUNK},
     {"HB_DIGEST_CACHE_MIB", HB_SW_DIGEST_CACHE},
+    {"HB_TEST_BATCH_BLOCKS", HB_SW_BATCH_BLOCKS},
 };
 
 int nl_for_bits(int bits) {
@@ -1601,6 +1608,210 @@ int encode_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &p
     return 0;
 }
 
+// ------------------------------------------------------------------ batched encode
+// hb_encode_many: the files of a batch, each under its own f_key and
+// alpha_key, in groups of one PRF launch (hb_batch_prf_kernel: a queue of
+// wave-jobs, 16 evaluations of one file under one key each) and one MAC launch
+// (hb_batch_mac_split_kernel / hb_batch_mac_kernel, the VALU MAC for every
+// limb count).  A group's device scratch -- key schedules, file, wave-job and
+// workgroup tables, the host files' bytes, F values, alpha tables, host-bound
+// tags -- is one arena (c->bdev) whose head (tables | files) mirrors the
+// pinned staging buffer, so a group costs one H2D copy and one D2H copy.
+// Groups end at HB_BATCH_BYTES of scratch ($HB_TEST_BATCH_BLOCKS, test
+// switch: at that many blocks).  Files with more blocks than the single-file
+// encode's quad-engine paths take (mid_max, encode_impl; or the test switch's
+// count) go through encode_impl after the groups.
+#define HB_BATCH_BYTES (1ull << 30)
+
+template <int NL>
+int encode_many_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &pi, u32 S, size_t key_len,
+                     const hb_file_desc *files, u64 nfiles, u32 flags, u64 *tries_out) {
+    const Limbs p = from_be(p_be, p_len, NL);
+    const u64 C = (u64)pi.ss * S;
+    const bool data_dev = flags & HB_DATA_ON_DEVICE, tags_dev = flags & HB_TAGS_ON_DEVICE;
+    const u64 mid_max = (NL <= 8 ? 17ull : 16ull) * 256ull * (u64)c->num_cus;
+    u64 cap_blocks = ~0ull;
+    if (const char *v = sw_env(c, "HB_TEST_BATCH_BLOCKS")) {
+        cap_blocks = strtoull(v, nullptr, 10);
+        if (cap_blocks < 1) cap_blocks = 1;
+    }
+    const u64 bound = cap_blocks < mid_max ? cap_blocks : mid_max;
+    // what every key schedule of the batch shares: R = p, nb, topmask
+    PrfParams<NL> P0;
+    int nr = 0;
+    if (!make_prf<NL>(files[0].f_key, key_len, p_be, p_len, P0, nr)) return fail(c, HB_EINVAL, "invalid key");
+    memset(P0.rk, 0, sizeof P0.rk);
+    memset(P0.r1z, 0, sizeof P0.r1z);   // (first-try constants of the lane engine: the quad engine has none)
+    const u32 bpw = hb_batch_mac_bpw<NL>(S);
+    const u64 na = ((u64)S + 15) / 16;   // alpha wave-jobs per file
+    auto up16 = [](u64 x) { return (x + 15) & ~15ull; };
+    auto blocks_of = [&](u64 i) { return files[i].len / C + 1; };
+    // scratch bytes of file i inside a group
+    auto cost_of = [&](u64 i) {
+        const u64 nb = blocks_of(i);
+        return 2 * sizeof(PrfParams<NL>) + sizeof(BatchFile) + (na + (nb + 15) / 16) * sizeof(BatchWaveJob) +
+               ((nb + bpw - 1) / bpw) * sizeof(BatchMacWg) + (data_dev ? 0 : up16(files[i].len)) + nb * NL * 4 +
+               (u64)S * NL * 4 + (tags_dev ? 0 : up16(nb * pi.tw));
+    };
+    unsigned long long *q0 = c->queue;
+    u64 tries = 0;
+    c->last_launches = 0;
+    c->last_ms = 0.0;
+    c->ph_valid = false;
+
+    auto run_group = [&](const std::vector<u64> &g, u64 blocks) -> int {
+        const u64 nf = g.size();
+        u64 nj = 0, nwg = 0, dbytes = 0, tbytes = 0;
+        for (u64 i : g) {
+            const u64 nb = blocks_of(i);
+            nj += na + (nb + 15) / 16;
+            nwg += (nb + bpw - 1) / bpw;
+            if (!data_dev) dbytes += up16(files[i].len);
+            if (!tags_dev) tbytes += up16(nb * pi.tw);
+        }
+        // arena: [prf | files | jobs | wgs | host files] (uploaded) [F | alpha | tags]
+        const u64 o_prf = 0, o_files = up16(o_prf + 2 * nf * sizeof(PrfParams<NL>));
+        const u64 o_jobs = up16(o_files + nf * sizeof(BatchFile)), o_wgs = up16(o_jobs + nj * sizeof(BatchWaveJob));
+        const u64 o_data = up16(o_wgs + nwg * sizeof(BatchMacWg)), up_bytes = o_data + dbytes;
+        const u64 o_fv = up_bytes, o_am = up16(o_fv + blocks * NL * 4), o_tags = up16(o_am + nf * S * NL * 4);
+        const u64 total = o_tags + tbytes;
+        HB_CHECK(c->bdev.ensure((size_t)total), "hipMalloc(batch)");
+        HB_CHECK(c->bhost.ensure((size_t)(up_bytes > tbytes ? up_bytes : tbytes)), "hipHostMalloc(batch)");
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        PrfParams<NL> *hprf = (PrfParams<NL> *)(host + o_prf);
+        BatchFile *hfiles = (BatchFile *)(host + o_files);
+        BatchWaveJob *hjobs = (BatchWaveJob *)(host + o_jobs);
+        BatchMacWg *hwgs = (BatchMacWg *)(host + o_wgs);
+        u64 fbase = 0, doff = o_data, toff = o_tags, j = 0, w = 0;
+        for (u64 f = 0; f < nf; ++f) {
+            const hb_file_desc &D = files[g[f]];
+            const u64 nb = blocks_of(g[f]);
+            const uint8_t *keys[2] = {D.f_key, D.alpha_key};
+            for (int k = 0; k < 2; ++k) {
+                AesKey ak;
+                if (!aes_expand(keys[k], key_len, ak)) return fail(c, HB_EINVAL, "invalid key");
+                hprf[2 * f + k] = P0;
+                memcpy(hprf[2 * f + k].rk, ak.rk, sizeof(u32) * 4 * (size_t)(ak.nr + 1));
+            }
+            BatchFile &F = hfiles[f];
+            memset(&F, 0, sizeof F);
+            if (data_dev) {
+                F.data = D.data;
+            } else {
+                // a file's len alone decides what is data: the padding up to
+                // the next file is never read as sector bytes
+                if (D.len) memcpy(host + doff, D.data, (size_t)D.len);
+                F.data = dev + doff;
+                doff += up16(D.len);
+            }
+            F.len = D.len;
+            if (tags_dev) {
+                F.tags = D.tags;
+            } else {
+                F.tags = dev + toff;
+                toff += up16(nb * pi.tw);
+            }
+            F.fbase = fbase;
+            F.nblocks = (u32)nb;
+            F.flags = (full16(pi, NL, C, F.data) ? HB_BF_LOAD16 : 0u) | ((uintptr_t)F.tags % 4 == 0 ? HB_BF_TAGS4 : 0u);
+            fbase += nb;
+            // the file's alpha wave-jobs, then its F wave-jobs: alpha and F
+            // of all files interleave in the queue, so no file's alpha waits
+            // behind every F chain
+            for (u64 a = 0; a < S; a += 16) hjobs[j++] = BatchWaveJob{(u32)f, 1u, (u32)a, (u32)(S - a < 16 ? S - a : 16)};
+            for (u64 b = 0; b < nb; b += 16) hjobs[j++] = BatchWaveJob{(u32)f, 0u, (u32)b, (u32)(nb - b < 16 ? nb - b : 16)};
+            for (u64 b = 0; b < nb; b += bpw) hwgs[w++] = BatchMacWg{(u32)f, (u32)b};
+        }
+        if (j != nj || w != nwg || fbase != blocks) return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        HB_CHECK(hipMemcpyAsync(dev, host, (size_t)up_bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(H2D batch)");
+        // slots 0 (wave-job counter, F tries) and 1 (alpha)
+        HB_CHECK(hipMemsetAsync(q0, 0, 2 * HB_QSLOT * sizeof(unsigned long long), c->stream), "hipMemsetAsync");
+        BatchPrfArgs<NL> A;
+        memset(&A, 0, sizeof A);
+        A.prf = (const PrfParams<NL> *)(dev + o_prf);
+        A.files = (const BatchFile *)(dev + o_files);
+        A.jobs = (const BatchWaveJob *)(dev + o_jobs);
+        A.njobs = nj;
+        make_mod<NL>(p, A.mod);
+        const Limbs &r2 = r2_of(c, p, NL);
+        for (int t = 0; t < NL; ++t) A.r2[t] = r2[t];
+        A.fv = (u32 *)(dev + o_fv);
+        A.amont = (u32 *)(dev + o_am);
+        A.S = S;
+        A.t0 = c->t0;
+        A.queue = q0;
+        const u64 waves = (nj + 15) / 16;
+        const int grid = (int)(waves < (u64)c->num_cus ? waves : (u64)c->num_cus);
+        HB_CHECK(hb_launch_batch_prf<NL>(A, nr, grid, c->stream), "hb_batch_prf_kernel launch");
+        BatchMacArgs<NL> M;
+        memset(&M, 0, sizeof M);
+        M.mod = A.mod;
+        M.files = A.files;
+        M.wgs = (const BatchMacWg *)(dev + o_wgs);
+        M.fv = A.fv;
+        M.amont = A.amont;
+        M.C = C;
+        M.ss = pi.ss;
+        M.S = S;
+        M.tw = pi.tw;
+        HB_CHECK(hb_launch_batch_mac<NL>(M, (u32)nwg, c->stream), "hb_batch_mac_kernel launch");
+        c->last_launches += 2;
+        unsigned long long qs[2 * HB_QSLOT];
+        if (!tags_dev)
+            HB_CHECK(hipMemcpyAsync(host, dev + o_tags, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream),
+                     "hipMemcpyAsync(D2H tags)");
+        HB_CHECK(hipMemcpyAsync(qs, q0, sizeof qs, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(queue)");
+        HB_CHECK(hipStreamSynchronize(c->stream), "batched encode");
+        if (qs[2] || qs[HB_QSLOT + 2]) return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate for some blocks");
+        tries += qs[1];
+        if (!tags_dev) {
+            u64 off = 0;
+            for (u64 i : g) {
+                const u64 n = blocks_of(i) * pi.tw;
+                memcpy(files[i].tags, host + off, (size_t)n);
+                off += up16(n);
+            }
+        }
+        return 0;
+    };
+
+    std::vector<u64> big, g;
+    int rc = 0;
+    for (u64 i = 0; i < nfiles && !rc;) {
+        g.clear();
+        u64 blocks = 0, bytes = 0;
+        for (; i < nfiles; ++i) {
+            const u64 nb = blocks_of(i);
+            if (nb > bound) {
+                big.push_back(i);
+                continue;
+            }
+            const u64 cost = cost_of(i);
+            if (!g.empty() && (nb > cap_blocks - blocks || bytes + cost > HB_BATCH_BYTES)) break;
+            g.push_back(i);
+            blocks += nb;
+            bytes += cost;
+        }
+        if (!g.empty()) rc = run_group(g, blocks);
+    }
+    // the slots as the other entry points expect them between calls
+    (void)hipMemsetAsync(q0, 0, 2 * HB_QSLOT * sizeof(unsigned long long), c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    for (u64 i : big) {
+        u64 t = 0;
+        rc = encode_impl<NL>(c, p_be, p_len, pi, S, files[i].f_key, files[i].alpha_key, key_len, 0, files[i].data,
+                             files[i].len, blocks_of(i), files[i].tags, flags & (HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE), &t);
+        if (rc) return rc;
+        tries += t;
+    }
+    HB_CHECK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    if (tries_out) *tries_out = tries;
+    return 0;
+}
+
 // ------------------------------------------------------------------ sums
 // Column counters (ncols + 1) and the index flag word of hb_wsum_kernel,
 // zero on allocation; the kernels leave them zero.
@@ -2362,12 +2573,13 @@ void hb_ctx_destroy(hb_ctx *c) {
     DevBuf *bufs[] = {&c->alpha_raw, &c->alpha_mont, &c->xs, &c->vals, &c->vals2, &c->wts, &c->idx,
                       &c->partials, &c->sums, &c->data[0], &c->data[1], &c->tags, &c->blen, &c->gtags,
                       &c->pfx, &c->retry, &c->ctl, &c->afrag, &c->mseeds, &c->moffs, &c->mdig, &c->gdev,
-                      &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig};
+                      &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig, &c->bdev};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
     c->gstage[1].release();
     c->hscratch.release();
+    c->bhost.release();
     if (c->t0) (void)hipFree(c->t0);
     if (c->queue) (void)hipFree(c->queue);
     if (c->k0) (void)hipEventDestroy(c->k0);
@@ -2619,6 +2831,37 @@ int hb_encode(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors,
     case 32: return encode_impl<32>(c, p_be, p_len, pi, sectors, f_key, alpha_key, key_len, block_base, data, len, nblocks, tags, flags, tries_out);
 #if !defined(HB_NO_NL64)
     default: return encode_impl<64>(c, p_be, p_len, pi, sectors, f_key, alpha_key, key_len, block_base, data, len, nblocks, tags, flags, tries_out);
+#else
+    default: return fail(c, HB_EUNSUPPORTED, "primes above 1024 bits: not in this build");
+#endif
+    }
+}
+
+int hb_encode_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors, size_t key_len,
+                   const hb_file_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    PrimeInfo pi;
+    if (int rc = parse_prime(c, p_be, p_len, pi)) return rc;
+    if (int rc = check_key(c, key_len)) return rc;
+    if (sectors == 0) return fail(c, HB_EINVAL, "sectors must be positive");
+    if (flags & (HB_PRF_CXX | HB_ASYNC | HB_ENCODE_SINGLE_PASS))
+        return fail(c, HB_EUNSUPPORTED, "hb_encode_many takes no HB_PRF_CXX, HB_ASYNC or HB_ENCODE_SINGLE_PASS");
+    if (tries_out) *tries_out = 0;
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "files is NULL");
+    for (u64 i = 0; i < nfiles; ++i) {
+        if (!files[i].f_key || !files[i].alpha_key) return fail(c, HB_EINVAL, "a file's key is NULL");
+        if (!files[i].tags) return fail(c, HB_EINVAL, "tags buffer is NULL");
+        if (!files[i].data && files[i].len) return fail(c, HB_EINVAL, "data buffer is NULL");
+    }
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    switch (pi.nl) {
+    case 8: return encode_many_impl<8>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+    case 16: return encode_many_impl<16>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+    case 32: return encode_many_impl<32>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+#if !defined(HB_NO_NL64)
+    default: return encode_many_impl<64>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
 #else
     default: return fail(c, HB_EUNSUPPORTED, "primes above 1024 bits: not in this build");
 #endif

@@ -128,6 +128,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_WIDE_SYNC_ALPHA 2097152u /* HB_WIDE_SYNC_ALPHA: the split encode computes alpha and its digit table on the compute stream, before the PRF passes, instead of beside them */
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
+#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many puts at most n blocks into one pair of launches, and files of more than n blocks go to the single-file encode */
 uint32_t hb_test_switches(void);
 
 /* Number of visible HIP devices (multi-GPU sharding of encode / prove opens
@@ -251,6 +252,37 @@ int hb_encode(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
               uint64_t block_base, const uint8_t *data, uint64_t len,
               uint64_t nblocks, uint8_t *tags, uint32_t flags,
               uint64_t *tries_out);
+
+/* Swizzle encode of many whole files, each under its own keys, in one call.
+ * Replaces a caller's loop over heartbeat/PySwizzle/PySwizzle.py:279-311
+ * (PySwizzle.encode draws a fresh f_key and alpha_key per file, :281): file
+ * i's tags are exactly what hb_encode writes for it with block_base = 0 and
+ * nblocks = hb_block_count(p, sectors, len) (a file with len == 0 has one
+ * block, tag = F(0)), PySwizzle's KeyedPRF.  One prime, one `sectors` and one
+ * key_len (16, 24 or 32) for the batch; keys, data, length and tag buffer per
+ * file.  A small file is bound by the latency of its longest PRF rejection
+ * chain, not by throughput: the batch runs the chains of all files side by
+ * side -- one PRF launch and one MAC launch per group of files (the runtime
+ * splits a batch whose device scratch would pass its cap) -- and files with
+ * more blocks than that path takes go through the single-file encode inside
+ * the same call, so any mix of sizes is accepted.
+ * flags: HB_DATA_ON_DEVICE / HB_TAGS_ON_DEVICE (device pointers of any
+ * alignment); HB_HOST_REGISTER is ignored; HB_PRF_CXX, HB_ASYNC and
+ * HB_ENCODE_SINGLE_PASS return HB_EUNSUPPORTED.  Host files go up in one copy
+ * from a pinned staging buffer, the tags come back in one.  nfiles == 0
+ * returns HB_OK.  *tries_out (may be NULL) receives the sum of the files' F
+ * tries: what nfiles hb_encode calls report in total. */
+typedef struct hb_file_desc {
+    const uint8_t *f_key, *alpha_key;  /* key_len bytes each */
+    const uint8_t *data;               /* host, or device with HB_DATA_ON_DEVICE; may be NULL when len == 0 */
+    uint64_t len;
+    uint8_t *tags;                     /* hb_block_count(p, sectors, len) * hb_width(p) bytes;
+                                          host, or device with HB_TAGS_ON_DEVICE */
+} hb_file_desc;
+
+int hb_encode_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                   size_t key_len, const hb_file_desc *files, uint64_t nfiles,
+                   uint32_t flags, uint64_t *tries_out);
 
 /* The cxx prf, prf::evaluate(i) (cxx/prf.hxx:125-145), for n unsigned-int
  * inputs, keyed by key and bounded by limit (any limit up to 2048 bits; when
