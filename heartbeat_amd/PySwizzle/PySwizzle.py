@@ -14,6 +14,7 @@ Same class names, constructor arguments, method signatures, defaults,
         gen_challenge(state) -> Challenge         PySwizzle.py:316-331
         prove(file, chal, tag) -> Proof           PySwizzle.py:333-370
         verify(proof, chal, state) -> bool        PySwizzle.py:372-395
+        verify_many(items) -> [bool]              a loop over :372-395, one GPU call
 
 Tags produced by encode keep their fixed-width big-endian image (``Tag.raw``)
 so prove can hand them to the GPU without converting 2^27 Python ints; the
@@ -362,6 +363,47 @@ class PySwizzle(object):
                                                   vmax, len(vmax), mub, rhs))
         return proof.sigma == int.from_bytes(rhs.raw, "big")
 
+    def verify_many(self, items):
+        """verify() of every (proof, chal, state) of `items` in one batched
+        GPU call (hb_verify_rhs_many): [bool, ...], exactly what a loop of
+        verify() (PySwizzle.py:372-395) returns, and the same HeartbeatError
+        at the first item a loop would raise it for (bad signature, too few
+        mu values, a state without chunks).  Every item is checked before any
+        GPU work, so a failing item costs no launch.  Items whose key lengths
+        differ from the batch's majority go through verify() one by one, and
+        so does a batch of fewer than VERIFY_MANY_MIN items."""
+        items = list(items)
+        p = int(self.prime)
+        S = int(self.sectors)
+        pre = []
+        for proof, chal, state in items:
+            state.decrypt(self.key)
+            self._check()
+            chunks = int(chal.chunks)
+            if chunks > 0 and int(state.chunks) <= 0:
+                raise HeartbeatError("state has no chunks")
+            mu = list(proof.mu)
+            if len(mu) < S:
+                raise HeartbeatError("proof has fewer than %d mu values" % S)
+            pre.append((_kb(state.f_key), _kb(state.alpha_key), int(state.chunks), _kb(chal.key),
+                        max(chunks, 0), int(chal.v_max) if chunks > 0 else 1, mu[:S]))
+        if not pre:
+            return []
+        lens = [(len(t[0]), len(t[1]), len(t[3])) for t in pre]
+        major = max(set(lens), key=lens.count)
+        batch = [i for i, kl in enumerate(lens) if kl == major and kl[0] == kl[1]]
+        if len(batch) < VERIFY_MANY_MIN:
+            batch = []
+        out = [None] * len(items)
+        if batch:
+            rhs = verify_rhs_many(p, S, [pre[i] for i in batch])
+            for i, r in zip(batch, rhs):
+                out[i] = items[i][0].sigma == r
+        for i, (proof, chal, state) in enumerate(items):
+            if out[i] is None:
+                out[i] = self.verify(proof, chal, state)
+        return out
+
     @staticmethod
     def tag_type():
         return Tag
@@ -475,6 +517,65 @@ def encode_files(p, sectors, keys, files):
         for fb in fbs:
             fb.close()
     return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+
+
+# Fewest proofs PySwizzle.verify_many sends through hb_verify_rhs_many; below
+# it the items go through verify() one by one.  One proof through the batch's
+# two launches loses to the fused single launch (1024-bit, S = 10, 820 chunks:
+# 1.07-1.10 against 0.90-0.94 ms; 256-bit, 129 chunks: 0.149-0.154 against
+# 0.096-0.098), two proofs already win (1.08-1.15 against 1.92-1.99 ms;
+# 0.150-0.172 against 0.193-0.196): scripts/verify_many_rate.py,
+# profiles/many/verify_many_rate.json, DESIGN.md 5.3b.
+VERIFY_MANY_MIN = 2
+
+
+def verify_rhs_many(p, sectors, items):
+    """Batched right-hand sides (hb_verify_rhs_many) of many proofs: `items`
+    is a list of (f_key, alpha_key, state_chunks, chal_key, chunks, v_max,
+    mu_list) with decrypted state keys; returns the list of ints that
+    hb_verify_rhs gives per item (PySwizzle.py:381-394).  All f_keys and
+    alpha_keys of a batch have one length, all challenge keys one length.  Runs
+    on multi.primary_context() (a batch is not spread over several GPUs)."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    if p.bit_length() // 8 < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if S < 1:
+        raise HeartbeatError("sectors must be positive")
+    w = _native.width_of(p)
+    keep = []
+    for fk, ak, nstate, ck, chunks, v_max, mu in items:
+        mu = list(mu)
+        if len(mu) < S:
+            raise HeartbeatError("proof has fewer than %d mu values" % S)
+        chunks = max(int(chunks), 0)
+        keep.append((_kb(fk), _kb(ak), _kb(ck), int(nstate), chunks,
+                     _native.be(int(v_max)) if chunks > 0 else b"\x01",
+                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu[:S])))
+    if len({len(t[0]) for t in keep} | {len(t[1]) for t in keep}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if len({len(t[2]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    descs = (_native.VerifyDesc * len(keep))()
+    out = ctypes.create_string_buffer(w * len(keep))
+    base = ctypes.addressof(out)
+    for i, (fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
+        d = descs[i]
+        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
+        d.state_chunks, d.chunks = nstate, chunks
+        d.vmax_be, d.vmax_len = vmax, len(vmax)
+        d.mu = mub
+        d.rhs_out = base + i * w
+    ctx = multi.primary_context()
+    pb = _native.be(p)
+    with ctx.lock:
+        ctx.check(_native.lib().hb_verify_rhs_many(ctx.h, pb, len(pb), S, len(keep[0][0]), len(keep[0][2]),
+                                                   descs, len(keep), 0))
+    raw = out.raw
+    return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
 
 
 # The reference's module path (heartbeat/PySwizzle/PySwizzle.py): pickles of

@@ -42,6 +42,14 @@ class FileDesc(ctypes.Structure):
                 ("len", ctypes.c_uint64), ("tags", ctypes.c_void_p)]
 
 
+class VerifyDesc(ctypes.Structure):
+    """hb_verify_desc (hbswizzle.h): one proof of an hb_verify_rhs_many batch."""
+    _fields_ = [("f_key", ctypes.c_char_p), ("alpha_key", ctypes.c_char_p), ("chal_key", ctypes.c_char_p),
+                ("state_chunks", ctypes.c_uint64), ("chunks", ctypes.c_uint64),
+                ("vmax_be", ctypes.c_char_p), ("vmax_len", ctypes.c_uint64),
+                ("mu", ctypes.c_char_p), ("rhs_out", ctypes.c_void_p)]
+
+
 SIGNATURES = [
     ("hb_abi_version", _c.c_int, []),
     ("hb_build_flags", _c.c_int, []),
@@ -70,6 +78,8 @@ SIGNATURES = [
     ("hb_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                  _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                  _B, _P]),
+    ("hb_verify_rhs_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.c_size_t,
+                                      _c.POINTER(VerifyDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_cxx_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                      _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                      _B, _P]),

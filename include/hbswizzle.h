@@ -129,6 +129,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
 #define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many puts at most n blocks into one pair of launches, and files of more than n blocks go to the single-file encode */
+#define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many puts at most n challenge indices into one pair of launches, and proofs of more than n chunks go to the single verify */
 uint32_t hb_test_switches(void);
 
 /* Number of visible HIP devices (multi-GPU sharding of encode / prove opens
@@ -342,6 +343,42 @@ int hb_verify_rhs(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t secto
                   const uint8_t *chal_key, size_t chal_key_len, uint64_t chunks,
                   const uint8_t *vmax_be, size_t vmax_len,
                   const uint8_t *mu, uint8_t *rhs_out);
+
+/* The right-hand sides of many proofs, each under its own keys, in one call.
+ * Replaces an auditor's loop of hb_verify_rhs over the proofs that came back
+ * for its challenges (PySwizzle.py:381-394 per proof): proof i's rhs_out
+ * receives exactly the bytes hb_verify_rhs writes for the same arguments,
+ * PySwizzle's KeyedPRF.  One prime, one `sectors`, one key_len and one
+ * chal_key_len (16, 24 or 32 each) for the batch; the state's keys and chunk
+ * count, the challenge's key, chunk count and v_max, mu and the result buffer
+ * per proof; all buffers are host memory.  A single verify is bound by the
+ * latency of its longest PRF rejection chain on a few dozen waves; the batch
+ * runs the chains of all proofs side by side -- one PRF launch and one sum
+ * launch per group of proofs (the runtime splits a batch whose device scratch
+ * would pass its cap) -- and proofs that path does not take (more challenge
+ * indices than the quad engine places, or key_len and chal_key_len with
+ * different AES round counts) go through the single verify inside the same
+ * call, so any mix is accepted and the results are the same.
+ * flags must be 0 (anything else returns HB_EUNSUPPORTED).  nproofs == 0
+ * returns HB_OK.  A descriptor that hb_verify_rhs would reject (state_chunks
+ * == 0 with chunks > 0, v_max == 0 with chunks > 0, a v_max wider than the
+ * prime's limb count, a NULL buffer) fails the whole call with the code
+ * hb_verify_rhs returns, before any GPU work, and hb_last_error names the
+ * proof's index.  The mu values go up and the results come back in one copy
+ * each per group. */
+typedef struct hb_verify_desc {        /* nine 8-byte words, in this order */
+    const uint8_t *f_key, *alpha_key;  /* key_len bytes each (decrypted state) */
+    const uint8_t *chal_key;           /* chal_key_len bytes */
+    uint64_t state_chunks, chunks;
+    const uint8_t *vmax_be;            /* may be NULL when chunks == 0 */
+    uint64_t vmax_len;
+    const uint8_t *mu;                 /* sectors * hb_width(p) bytes */
+    uint8_t *rhs_out;                  /* hb_width(p) bytes */
+} hb_verify_desc;
+
+int hb_verify_rhs_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                       size_t key_len, size_t chal_key_len,
+                       const hb_verify_desc *proofs, uint64_t nproofs, uint32_t flags);
 
 /* Right-hand side of the cxx extension's verify (shacham_waters_private.cxx:
  * 791-842) for a decrypted state: the same sum as hb_verify_rhs with the cxx
