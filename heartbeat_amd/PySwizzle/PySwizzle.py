@@ -338,6 +338,49 @@ class PySwizzle(object):
             fb.close()
         return proof
 
+    def prove_many(self, items):
+        """prove() of every (file, chal, tag) of `items` in one batched GPU
+        call (hb_prove_many): [Proof, ...], exactly what a loop of prove()
+        (PySwizzle.py:333-370) returns -- a zero proof for chunks <= 0 -- and
+        HeartbeatError("tag is empty") at the first item a loop would raise it
+        for.  Every item is checked before any GPU work, so a failing item
+        costs no launch.  Items whose key length differs from the batch's
+        majority go through prove() one by one, and so do challenges that
+        prove() would shard over several GPUs and a batch of fewer than
+        PROVE_MANY_MIN items."""
+        items = list(items)
+        p = int(self.prime)
+        S = int(self.sectors)
+        out = [None] * len(items)
+        cand = []
+        for i, (file, chal, tag) in enumerate(items):
+            self._check()
+            if int(chal.chunks) <= 0:
+                out[i] = Proof()
+                out[i].mu = [0] * S
+                out[i].sigma = 0
+            elif len(tag) == 0:
+                raise HeartbeatError("tag is empty")
+            else:
+                cand.append(i)
+        ndev = len(multi.devices())
+        lens = [len(_kb(items[i][1].key)) for i in cand]
+        major = max(set(lens), key=lens.count) if lens else 0
+        batch = [i for i, kl in zip(cand, lens) if kl == major and
+                 multi.shard_count(ndev, int(items[i][1].chunks), multi.MIN_SHARD_CHUNKS) == 1]
+        if len(batch) < PROVE_MANY_MIN:
+            batch = []
+        if batch:
+            res = prove_files(p, S, [(items[i][1].key, int(items[i][1].chunks), int(items[i][1].v_max),
+                                      items[i][2], items[i][0]) for i in batch])
+            for i, (mu, sigma) in zip(batch, res):
+                out[i] = Proof()
+                out[i].mu, out[i].sigma = mu, sigma
+        for i, (file, chal, tag) in enumerate(items):
+            if out[i] is None:
+                out[i] = self.prove(file, chal, tag)
+        return out
+
     def verify(self, proof, chal, state):
         """True iff proof.sigma == sum v_i F(idx_i) + sum alpha_j mu_j mod p."""
         state.decrypt(self.key)
@@ -517,6 +560,77 @@ def encode_files(p, sectors, keys, files):
         for fb in fbs:
             fb.close()
     return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+
+
+# Fewest proofs PySwizzle.prove_many sends through hb_prove_many; below it the
+# items go through prove() one by one.  One proof through the batch's three
+# launches only ties with the single fused launch (1024-bit, S = 10, 820
+# chunks of a 1 MiB host file: 0.81-0.85 against 0.82-0.86 ms), two proofs
+# already win (1.01-1.10 against 1.80-1.84 ms), three by 2.3x:
+# scripts/prove_many_rate.py, profiles/many/prove_many_rate.json, DESIGN.md 5.3c.
+PROVE_MANY_MIN = 2
+
+
+def prove_files(p, sectors, items):
+    """Batched GPU prove (hb_prove_many) of many challenges: `items` is a list
+    of (chal_key, chunks, v_max, tag, file) with a Tag and a file object /
+    buffer each; returns [(mu list, sigma), ...], what hb_prove gives per item
+    (PySwizzle.py:333-370).  Every file is read whole, from its start, and its
+    position is left where it was, as by PySwizzle.prove.  All challenge keys
+    of a batch have one length.  Runs on multi.primary_context() (a batch is
+    not spread over several GPUs)."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    if p.bit_length() // 8 < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if S < 1:
+        raise HeartbeatError("sectors must be positive")
+    keep = []
+    for ck, chunks, v_max, tag, file in items:
+        if len(tag) == 0:
+            raise HeartbeatError("tag is empty")
+        chunks = max(int(chunks), 0)
+        keep.append((_kb(ck), chunks, _native.be(int(v_max)), tag, file))
+    if len({len(t[0]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    w = _native.width_of(p)
+    n = len(keep)
+    descs = (_native.ProveDesc * n)()
+    out = ctypes.create_string_buffer((S + 1) * w * n)
+    base = ctypes.addressof(out)
+    fbs, tarrs = [], []
+    try:
+        for i, (ck, chunks, vmax, tag, file) in enumerate(keep):
+            # absolute offsets from the start of the file, as the reference's
+            # file.seek(pos) before every read (PySwizzle.py:353-355)
+            fb = FileBuffer(file, from_start=True)
+            fbs.append(fb)
+            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
+            tarrs.append(tarr)
+            d = descs[i]
+            d.chal_key, d.chunks = ck, chunks
+            d.vmax_be, d.vmax_len = vmax, len(vmax)
+            d.tags, d.ntags = tarr.ctypes.data, len(tag)
+            d.data, d.len = fb.addr, fb.len
+            d.mu_out = base + i * (S + 1) * w
+            d.sigma_out = base + (i * (S + 1) + S) * w
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        with ctx.lock:
+            ctx.check(_native.lib().hb_prove_many(ctx.h, pb, len(pb), S, len(keep[0][0]), descs, n, 0))
+    finally:
+        for fb in fbs:
+            fb.restore()
+            fb.close()
+    raw = out.raw
+    res = []
+    for i in range(n):
+        vals = [int.from_bytes(raw[(i * (S + 1) + j) * w:(i * (S + 1) + j + 1) * w], "big") for j in range(S + 1)]
+        res.append((vals[:S], vals[S]))
+    return res
 
 
 # Fewest proofs PySwizzle.verify_many sends through hb_verify_rhs_many; below

@@ -50,6 +50,15 @@ class VerifyDesc(ctypes.Structure):
                 ("mu", ctypes.c_char_p), ("rhs_out", ctypes.c_void_p)]
 
 
+class ProveDesc(ctypes.Structure):
+    """hb_prove_desc (hbswizzle.h): one proof of an hb_prove_many batch."""
+    _fields_ = [("chal_key", ctypes.c_char_p), ("chunks", ctypes.c_uint64),
+                ("vmax_be", ctypes.c_char_p), ("vmax_len", ctypes.c_uint64),
+                ("tags", ctypes.c_void_p), ("ntags", ctypes.c_uint64),
+                ("data", ctypes.c_void_p), ("len", ctypes.c_uint64),
+                ("mu_out", ctypes.c_void_p), ("sigma_out", ctypes.c_void_p)]
+
+
 SIGNATURES = [
     ("hb_abi_version", _c.c_int, []),
     ("hb_build_flags", _c.c_int, []),
@@ -75,6 +84,8 @@ SIGNATURES = [
     ("hb_prove_range", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _c.c_size_t, _c.c_uint64,
                                   _c.c_uint64, _c.c_uint64, _B, _c.c_size_t, _P, _c.c_uint64, _P,
                                   _c.c_uint64, _c.c_uint32, _P, _P]),
+    ("hb_prove_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(ProveDesc),
+                                 _c.c_uint64, _c.c_uint32]),
     ("hb_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                  _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                  _B, _P]),

@@ -129,7 +129,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
 #define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many puts at most n blocks into one pair of launches, and files of more than n blocks go to the single-file encode */
-#define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many puts at most n challenge indices into one pair of launches, and proofs of more than n chunks go to the single verify */
+#define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many and hb_prove_many put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
 uint32_t hb_test_switches(void);
 
 /* Number of visible HIP devices (multi-GPU sharding of encode / prove opens
@@ -332,6 +332,47 @@ int hb_prove_range(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sect
                    const uint8_t *tags, uint64_t ntags,
                    const uint8_t *data, uint64_t len, uint32_t flags,
                    uint8_t *mu_out, uint8_t *sigma_out);
+
+/* mu and sigma of many proofs, each under its own challenge key, file and tag
+ * array, in one call.  Replaces a storage node's loop of hb_prove over the
+ * challenges of an audit period (PySwizzle.py:333-370 per proof): proof i's
+ * mu_out and sigma_out receive exactly the bytes hb_prove writes for the same
+ * arguments, PySwizzle's KeyedPRF.  One prime, one `sectors` and one key_len
+ * (16, 24 or 32) for the batch; everything else per proof.  A single prove of
+ * a small file is bound by the latency of its longest PRF rejection chain on
+ * a few dozen waves; the batch runs the chains of all proofs side by side --
+ * per group of proofs one H2D copy, one PRF launch, a Montgomery pass over
+ * the group's v, one sum launch and one D2H copy (the runtime splits a batch
+ * whose device scratch, uploaded files included, would pass its cap).
+ * flags applies to the whole batch: HB_DATA_ON_DEVICE and/or
+ * HB_TAGS_ON_DEVICE (device pointers of any alignment); anything else
+ * (HB_PRF_CXX, HB_ASYNC, ...) returns HB_EUNSUPPORTED.  A host-resident file
+ * is batched when hb_prove would upload it whole (len <= max(2 chunks C,
+ * 8 MiB), C = sectors * sector size); its bytes and host tags go up in the
+ * group's one copy.  Proofs that path does not take (more challenge indices
+ * than the quad engine places, a larger host file, host data with device
+ * tags) go through the single prove inside the same call, so any mix is
+ * accepted and the results are the same.  chunks == 0 gives zero mu and
+ * sigma.  nproofs == 0 returns HB_OK.  A descriptor that hb_prove would
+ * reject (ntags == 0, v_max == 0, a v_max wider than the prime's limb count
+ * -- also with chunks == 0) fails the whole call with the code hb_prove
+ * returns, before any GPU work, and so does a NULL key, result buffer, tags,
+ * or data with len > 0 (HB_EINVAL); hb_last_error names the proof's index. */
+typedef struct hb_prove_desc {        /* ten 8-byte words, in this order */
+    const uint8_t *chal_key;          /* key_len bytes */
+    uint64_t chunks;
+    const uint8_t *vmax_be;
+    uint64_t vmax_len;
+    const uint8_t *tags;              /* ntags * hb_width(p) bytes; host, or device with HB_TAGS_ON_DEVICE */
+    uint64_t ntags;
+    const uint8_t *data;              /* the whole file; host, or device with HB_DATA_ON_DEVICE; may be NULL when len == 0 */
+    uint64_t len;
+    uint8_t *mu_out;                  /* sectors * hb_width(p) bytes, host */
+    uint8_t *sigma_out;               /* hb_width(p) bytes, host */
+} hb_prove_desc;
+
+int hb_prove_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                  size_t key_len, const hb_prove_desc *proofs, uint64_t nproofs, uint32_t flags);
 
 /* Right-hand side of PySwizzle.verify (PySwizzle.py:381-394) for a decrypted
  * state:  rhs = sum_i v_i * F(idx_i) + sum_j alpha(j) * mu_j  mod p.
