@@ -444,6 +444,30 @@ class Swizzle(_Serializable):
         state.encrypt(self.k_enc, self.k_mac)
         return Tag._from_raw(memoryview(out), w), state
 
+    def encode_many(self, files):
+        """[(Tag, State), ...] of every file of `files` in one batched GPU
+        call (hb_cxx_encode_many): exactly what a loop of encode() returns --
+        fresh keys per file, each state encrypted and signed, each file read
+        from its position to EOF and left there.  Fewer than
+        CXX_ENCODE_MANY_MIN files go through encode() one by one."""
+        self._check()
+        files = list(files)
+        if len(files) < CXX_ENCODE_MANY_MIN:
+            return [self.encode(f) for f in files]
+        states = []
+        for _ in files:
+            state = State()
+            state.f_key = _random_bytes(KEY_SIZE)
+            state.alpha_key = _random_bytes(KEY_SIZE)
+            states.append(state)
+        res = encode_files(self.prime, self.sectors, [(s.f_key, s.alpha_key) for s in states], files)
+        out = []
+        for state, (tag, nblocks) in zip(states, res):
+            state.n = nblocks
+            state.encrypt(self.k_enc, self.k_mac)
+            out.append((tag, state))
+        return out
+
     def gen_challenge(self, state):
         """l = (unsigned int)(check_fraction * n) indices, v limit p (:704-729)."""
         s = state._copy()   # `state s = s_enc` (:706)
@@ -527,6 +551,76 @@ class Swizzle(_Serializable):
     @staticmethod
     def proof_type():
         return Proof
+
+
+# Fewest files Swizzle.encode_many sends through hb_cxx_encode_many; below it
+# the files go through encode() one by one.  Already one file is ahead in the
+# batch's three launches (1024-bit, S = 10, 1 MiB: B's slowest round beats A's
+# fastest device-resident and from host memory, and by 2x and 3x at two and
+# three files: the 1-, 2- and 3-file rows of scripts/cxx_many_rate.py,
+# profiles/many/cxx_many_rate.json) -- the single cxx encode
+# is an alpha launch, a Montgomery pass and the engine launch with a
+# synchronise of its own -- so every non-empty list takes the batch.
+CXX_ENCODE_MANY_MIN = 1
+
+
+def encode_files(p, sectors, keys, files):
+    """Batched GPU encode (hb_cxx_encode_many) of many file objects / buffers
+    with the cxx prf, file i under keys[i] = (f_key, alpha_key): [(Tag, number
+    of blocks), ...].  Each file is read from its current position to EOF and
+    left there, as by Swizzle.encode; all keys of a batch have one length.
+    Every file is opened before any GPU work; if one cannot be read, the files
+    before it are left at EOF as the loop leaves them and its error is raised.
+    Runs on multi.primary_context() (a batch is not spread over several
+    GPUs)."""
+    p = int(p)
+    files = list(files)
+    keys = list(keys)
+    if len(keys) != len(files):
+        raise HeartbeatError("%d key pairs for %d files" % (len(keys), len(files)))
+    ss = p.bit_length() // 8
+    if ss < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if int(sectors) < 1:
+        raise HeartbeatError("sectors must be positive")
+    kb = [(_kb(fk), _kb(ak)) for fk, ak in keys]
+    if len({len(k) for pair in kb for k in pair}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if not files:
+        return []
+    w = _native.width_of(p)
+    C = ss * int(sectors)
+    fbs, outs = [], []
+    try:
+        descs = (_native.FileDesc * len(files))()
+        try:
+            for file in files:
+                fbs.append(FileBuffer(file))
+        except BaseException:
+            for fb in fbs:
+                fb.consume()
+            raise
+        for d, fb, (fk, ak) in zip(descs, fbs, kb):
+            nblocks = fb.len // C + 1
+            # the tags land in the array the Tag keeps
+            out = np.empty(nblocks * w, dtype=np.uint8)
+            outs.append((out, nblocks))
+            d.f_key, d.alpha_key = fk, ak
+            d.data = fb.addr
+            d.len = fb.len
+            d.tags = out.ctypes.data
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        tries = ctypes.c_uint64()
+        with ctx.lock:
+            ctx.check(_native.lib().hb_cxx_encode_many(ctx.h, pb, len(pb), int(sectors), len(kb[0][0]), descs,
+                                                       len(files), 0, ctypes.byref(tries)))
+        for fb in fbs:
+            fb.consume()
+    finally:
+        for fb in fbs:
+            fb.close()
+    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
 
 
 # The extension module's path (cxx/Swizzle.hxx:738, imported as

@@ -78,6 +78,8 @@ SIGNATURES = [
                              _c.POINTER(_c.c_uint64)]),
     ("hb_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
                                   _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_cxx_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
+                                      _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_block_count", _c.c_uint64, [_B, _c.c_size_t, _c.c_uint32, _c.c_uint64]),
     ("hb_prove", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _c.c_size_t, _c.c_uint64, _B,
                             _c.c_size_t, _P, _c.c_uint64, _P, _c.c_uint64, _c.c_uint32, _P, _P]),

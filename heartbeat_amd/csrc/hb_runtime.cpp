@@ -28,6 +28,7 @@
 #include "hb_wide_args.hpp"
 #include "hb_vbatch_args.hpp"
 #include "hb_pbatch_args.hpp"
+#include "hb_cbatch_args.hpp"
 #include "hb_bignum_host.hpp"
 
 using namespace hbhost;
@@ -58,6 +59,8 @@ template <int NL> hipError_t hb_launch_vbatch_sum(const VbSumArgs<NL> &, u32, hi
 // hb_kern_pbatch.hip / hb_kern_pbatch64.hip
 template <int NL> hipError_t hb_launch_pbatch_prf(const PbPrfArgs<NL> &, int, int, hipStream_t);
 template <int NL> hipError_t hb_launch_pbatch_sum(const PbSumArgs<NL> &, u32, hipStream_t);
+// hb_kern_cbatch.hip / hb_kern_cbatch64.hip
+template <int NL> hipError_t hb_launch_cbatch_prf(const CbPrfArgs<NL> &, int, int, hipStream_t);
 
 namespace {
 
@@ -1821,6 +1824,197 @@ int encode_many_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeIn
     return 0;
 }
 
+// ------------------------------------------------------------------ batched cxx encode
+// hb_cxx_encode_many: encode_many_impl for the cxx Swizzle (HB_PRF_CXX).  The
+// planner (hb_cbatch_plan.hpp, a pure host function) decides which files the
+// batch path takes, the groups and each group's queue of wave-jobs, longest
+// first; a group is the same arena and the same two copies as
+// encode_many_impl's, and three launches: hb_cbatch_prf_kernel (F of every
+// block, alpha of every sector, raw), hb_mont_kernel in place over the
+// group's alpha tables, and the batched encode's MAC kernel unchanged.  A
+// block that reads no sector keeps F unreduced (hb_cbatch_args.hpp): the PRF
+// launch stores that tag and the file's table entry ends before it.
+template <int NL>
+int cxx_encode_many_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &pi, u32 S, size_t key_len,
+                         const hb_file_desc *files, u64 nfiles, u32 flags, u64 *tries_out) {
+    const Limbs p = from_be(p_be, p_len, NL);
+    const u64 C = (u64)pi.ss * S;
+    const bool data_dev = flags & HB_DATA_ON_DEVICE, tags_dev = flags & HB_TAGS_ON_DEVICE;
+    // the files hb_encode_many batches
+    const u64 mid_max = (NL <= 8 ? 17ull : 16ull) * 256ull * (u64)c->num_cus;
+    u64 cap_blocks = ~0ull;
+    if (const char *v = sw_env(c, "HB_TEST_BATCH_BLOCKS")) {
+        cap_blocks = strtoull(v, nullptr, 10);
+        if (cap_blocks < 1) cap_blocks = 1;
+    }
+    const u64 bound = cap_blocks < mid_max ? cap_blocks : mid_max;
+    PrfParams<NL> P0;
+    int nr = 0;
+    if (!make_prf<NL>(files[0].f_key, key_len, p_be, p_len, P0, nr)) return fail(c, HB_EINVAL, "invalid key");
+    memset(P0.rk, 0, sizeof P0.rk);
+    memset(P0.r1z, 0, sizeof P0.r1z);   // (KeyedPRF's first-try constants)
+    const u32 bpw = hb_batch_mac_bpw<NL>(S);
+    auto up16 = [](u64 x) { return (x + 15) & ~15ull; };
+    auto blocks_of = [&](u64 i) { return files[i].len / C + 1; };
+    auto jobs_of = [](u64 n) { return (n + HB_CB_JOB - 1) / HB_CB_JOB; };
+    // blocks with a sector read: the MAC launch's
+    auto mac_blocks_of = [&](u64 i) { return files[i].len / C + (files[i].len % C ? 1 : 0); };
+    std::vector<HbCbItemReq> req((size_t)nfiles);
+    for (u64 i = 0; i < nfiles; ++i) {
+        const u64 nb = blocks_of(i);
+        HbCbItemReq &R = req[(size_t)i];
+        R.n[HB_CB_F] = nb;
+        R.n[HB_CB_ALPHA] = S;
+        R.aes[HB_CB_F] = R.aes[HB_CB_ALPHA] = pi.tw / 16;
+        R.units = nb;
+        R.bytes = 2 * sizeof(PrfParams<NL>) + sizeof(BatchFile) + (jobs_of(nb) + jobs_of(S)) * sizeof(HbCbJob) +
+                  ((mac_blocks_of(i) + bpw - 1) / bpw) * sizeof(BatchMacWg) + (data_dev ? 0 : up16(files[i].len)) +
+                  nb * NL * 4 + (u64)S * NL * 4 + (tags_dev ? 0 : up16(nb * pi.tw));
+    }
+    const HbCbPlan plan = hb_cbatch_plan(req.data(), nfiles, bound, cap_blocks, HB_BATCH_BYTES);
+    unsigned long long *q0 = c->queue;
+    u64 tries = 0;
+    c->last_launches = 0;
+    c->last_ms = 0.0;
+    c->ph_valid = false;
+
+    auto run_group = [&](const HbCbGroup &G) -> int {
+        const u64 nf = G.nitems, nj = G.njobs, blocks = G.units;
+        const u64 *g = plan.order.data() + G.item0;
+        u64 nwg = 0, dbytes = 0, tbytes = 0;
+        for (u64 f = 0; f < nf; ++f) {
+            nwg += (mac_blocks_of(g[f]) + bpw - 1) / bpw;
+            if (!data_dev) dbytes += up16(files[g[f]].len);
+            if (!tags_dev) tbytes += up16(blocks_of(g[f]) * pi.tw);
+        }
+        // arena: [prf | files | jobs | wgs | host files] (uploaded) [F | alpha | tags]
+        const u64 o_prf = 0, o_files = up16(o_prf + 2 * nf * sizeof(PrfParams<NL>));
+        const u64 o_jobs = up16(o_files + nf * sizeof(BatchFile)), o_wgs = up16(o_jobs + nj * sizeof(HbCbJob));
+        const u64 o_data = up16(o_wgs + nwg * sizeof(BatchMacWg)), up_bytes = o_data + dbytes;
+        const u64 o_fv = up_bytes, o_am = up16(o_fv + blocks * NL * 4), o_tags = up16(o_am + nf * S * NL * 4);
+        const u64 total = o_tags + tbytes;
+        HB_CHECK(c->bdev.ensure((size_t)total), "hipMalloc(batch)");
+        HB_CHECK(c->bhost.ensure((size_t)(up_bytes > tbytes ? up_bytes : tbytes)), "hipHostMalloc(batch)");
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        PrfParams<NL> *hprf = (PrfParams<NL> *)(host + o_prf);
+        BatchFile *hfiles = (BatchFile *)(host + o_files);
+        BatchMacWg *hwgs = (BatchMacWg *)(host + o_wgs);
+        u64 doff = o_data, toff = o_tags, w = 0;
+        for (u64 f = 0; f < nf; ++f) {
+            const hb_file_desc &D = files[g[f]];
+            const u64 nb = blocks_of(g[f]), mb = mac_blocks_of(g[f]);
+            const uint8_t *keys[2] = {D.f_key, D.alpha_key};   // HB_CB_F, HB_CB_ALPHA
+            for (int k = 0; k < 2; ++k) {
+                AesKey ak;
+                if (!aes_expand(keys[k], key_len, ak)) return fail(c, HB_EINVAL, "invalid key");
+                hprf[2 * f + k] = P0;
+                memcpy(hprf[2 * f + k].rk, ak.rk, sizeof(u32) * 4 * (size_t)(ak.nr + 1));
+            }
+            BatchFile &F = hfiles[f];
+            memset(&F, 0, sizeof F);
+            if (data_dev) {
+                F.data = D.data;
+            } else {
+                if (D.len) memcpy(host + doff, D.data, (size_t)D.len);
+                F.data = dev + doff;
+                doff += up16(D.len);
+            }
+            F.len = D.len;
+            if (tags_dev) {
+                F.tags = D.tags;
+            } else {
+                F.tags = dev + toff;
+                toff += up16(nb * pi.tw);
+            }
+            F.fbase = plan.ubase[(size_t)(G.item0 + f)];
+            F.nblocks = (u32)mb;
+            F.flags = (full16(pi, NL, C, F.data) ? HB_BF_LOAD16 : 0u) | ((uintptr_t)F.tags % 4 == 0 ? HB_BF_TAGS4 : 0u);
+            for (u64 b = 0; b < mb; b += bpw) hwgs[w++] = BatchMacWg{(u32)f, (u32)b};
+        }
+        if (w != nwg) return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        memcpy(host + o_jobs, plan.jobs.data() + G.job0, (size_t)(nj * sizeof(HbCbJob)));
+        HB_CHECK(hipMemcpyAsync(dev, host, (size_t)up_bytes, hipMemcpyHostToDevice, c->stream), "hipMemcpyAsync(H2D batch)");
+        // slots 0 (wave-job counter, F tries) and 1 (alpha tries)
+        HB_CHECK(hipMemsetAsync(q0, 0, 2 * HB_QSLOT * sizeof(unsigned long long), c->stream), "hipMemsetAsync");
+        CbPrfArgs<NL> A;
+        memset(&A, 0, sizeof A);
+        A.prf = (const PrfParams<NL> *)(dev + o_prf);
+        A.files = (const BatchFile *)(dev + o_files);
+        A.jobs = (const HbCbJob *)(dev + o_jobs);
+        A.njobs = nj;
+        A.fv = (u32 *)(dev + o_fv);
+        A.araw = (u32 *)(dev + o_am);
+        A.C = C;
+        A.S = S;
+        A.tw = pi.tw;
+        A.t0 = c->t0;
+        A.queue = q0;
+        // a workgroup per wave-job up to one per CU: the lookups of a CU's
+        // waves share its LDS, so a queue shorter than 16 x #CUs is spread
+        // over the CUs instead of filling the first ones with 16 waves each
+        const int grid = (int)(nj < (u64)c->num_cus ? nj : (u64)c->num_cus);
+        HB_CHECK(hb_launch_cbatch_prf<NL>(A, nr, grid, c->stream), "hb_cbatch_prf_kernel launch");
+        if (int rc = run_mont<NL>(c, p, A.araw, A.araw, nf * S)) return rc;
+        c->last_launches += 2;
+        if (nwg) {
+            BatchMacArgs<NL> M;
+            memset(&M, 0, sizeof M);
+            make_mod<NL>(p, M.mod);
+            M.files = A.files;
+            M.wgs = (const BatchMacWg *)(dev + o_wgs);
+            M.fv = A.fv;
+            M.amont = A.araw;
+            M.C = C;
+            M.ss = pi.ss;
+            M.S = S;
+            M.tw = pi.tw;
+            HB_CHECK(hb_launch_batch_mac<NL>(M, (u32)nwg, c->stream), "hb_batch_mac_kernel launch");
+            c->last_launches += 1;
+        }
+        unsigned long long qs[2 * HB_QSLOT];
+        if (!tags_dev)
+            HB_CHECK(hipMemcpyAsync(host, dev + o_tags, (size_t)tbytes, hipMemcpyDeviceToHost, c->stream),
+                     "hipMemcpyAsync(D2H tags)");
+        HB_CHECK(hipMemcpyAsync(qs, q0, sizeof qs, hipMemcpyDeviceToHost, c->stream), "hipMemcpyAsync(queue)");
+        HB_CHECK(hipStreamSynchronize(c->stream), "batched cxx encode");
+        tries += qs[1];
+        if (!tags_dev) {
+            u64 off = 0;
+            for (u64 f = 0; f < nf; ++f) {
+                const u64 n = blocks_of(g[f]) * pi.tw;
+                memcpy(files[g[f]].tags, host + off, (size_t)n);
+                off += up16(n);
+            }
+        }
+        return 0;
+    };
+
+    int rc = 0;
+    for (size_t k = 0; k < plan.groups.size() && !rc; ++k) rc = run_group(plan.groups[k]);
+    // the slots as the other entry points expect them between calls
+    (void)hipMemsetAsync(q0, 0, 2 * HB_QSLOT * sizeof(unsigned long long), c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    u32 launches = c->last_launches;   // (encode_impl counts its own from zero)
+    for (u64 i : plan.through) {
+        u64 t = 0;
+        rc = encode_impl<NL>(c, p_be, p_len, pi, S, files[i].f_key, files[i].alpha_key, key_len, 0, files[i].data,
+                             files[i].len, blocks_of(i), files[i].tags,
+                             (flags & (HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE)) | HB_PRF_CXX, &t);
+        if (rc) return rc;
+        tries += t;
+        launches += c->last_launches;
+    }
+    c->last_launches = launches;
+    c->last_ms = 0.0;
+    c->ph_valid = false;
+    HB_CHECK(hipStreamSynchronize(c->stream), "hipStreamSynchronize");
+    if (tries_out) *tries_out = tries;
+    return 0;
+}
+
 // ------------------------------------------------------------------ sums
 // Column counters (ncols + 1) and the index flag word of hb_wsum_kernel,
 // zero on allocation; the kernels leave them zero.
@@ -3339,6 +3533,41 @@ int hb_encode_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sector
     case 32: return encode_many_impl<32>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
 #if !defined(HB_NO_NL64)
     default: return encode_many_impl<64>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+#else
+    default: return fail(c, HB_EUNSUPPORTED, "primes above 1024 bits: not in this build");
+#endif
+    }
+}
+
+int hb_cxx_encode_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors, size_t key_len,
+                       const hb_file_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    PrimeInfo pi;
+    if (int rc = parse_prime(c, p_be, p_len, pi)) return rc;
+    if (int rc = check_key(c, key_len)) return rc;
+    if (sectors == 0) return fail(c, HB_EINVAL, "sectors must be positive");
+    if (flags & ~(uint32_t)(HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE))
+        return fail(c, HB_EUNSUPPORTED, "hb_cxx_encode_many takes HB_DATA_ON_DEVICE and HB_TAGS_ON_DEVICE only");
+    if (tries_out) *tries_out = 0;
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "files is NULL");
+    // what hb_encode(HB_PRF_CXX) rejects, for every file before any GPU work
+    for (u64 i = 0; i < nfiles; ++i) {
+        const std::string at = "file " + std::to_string(i) + ": ";
+        if (!files[i].f_key || !files[i].alpha_key) return fail(c, HB_EINVAL, at + "a key is NULL");
+        if (!files[i].tags) return fail(c, HB_EINVAL, at + "tags buffer is NULL");
+        if (!files[i].data && files[i].len) return fail(c, HB_EINVAL, at + "data buffer is NULL");
+    }
+    if (pi.tw % 16 != 0 || pi.tw > 4u * (u32)pi.nl)
+        return fail(c, HB_EUNSUPPORTED, "cxx prf mode needs ByteCount(p) to be a multiple of 16");
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    switch (pi.nl) {
+    case 8: return cxx_encode_many_impl<8>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+    case 16: return cxx_encode_many_impl<16>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+    case 32: return cxx_encode_many_impl<32>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+#if !defined(HB_NO_NL64)
+    default: return cxx_encode_many_impl<64>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
 #else
     default: return fail(c, HB_EUNSUPPORTED, "primes above 1024 bits: not in this build");
 #endif

@@ -128,7 +128,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_WIDE_SYNC_ALPHA 2097152u /* HB_WIDE_SYNC_ALPHA: the split encode computes alpha and its digit table on the compute stream, before the PRF passes, instead of beside them */
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
-#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many puts at most n blocks into one pair of launches, and files of more than n blocks go to the single-file encode */
+#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode */
 #define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many and hb_prove_many put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
 uint32_t hb_test_switches(void);
 
@@ -284,6 +284,34 @@ typedef struct hb_file_desc {
 int hb_encode_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
                    size_t key_len, const hb_file_desc *files, uint64_t nfiles,
                    uint32_t flags, uint64_t *tries_out);
+
+/* hb_encode_many for the cxx Swizzle (heartbeat.Heartbeat): many whole files,
+ * each under its own keys, in one call.
+ * Replaces a caller's loop over cxx/shacham_waters_private.cxx:638-702 with
+ * the prf of cxx/prf.hxx:125-176: file i's tags are exactly the bytes that
+ * hb_encode writes for it with HB_PRF_CXX, block_base = 0 and nblocks =
+ * hb_block_count(p, sectors, len) -- a block that reads no sector (the last
+ * one of a file whose length is a multiple of the block size; the only one of
+ * an empty file) keeps F as the prf returned it (:681-690).  Same descriptors
+ * as hb_encode_many; one prime, one `sectors` and one key_len for the batch.
+ * A try of the cxx prf is ByteCount(p) / 16 full AES blocks, so the single
+ * call is bound by its launches, not by a chain: here a group of files is one
+ * PRF launch (one lane per evaluation, wave-jobs of up to 64 evaluations of
+ * one file under one key, longest first), one Montgomery pass over the
+ * group's alpha values and one MAC launch, with one copy up and one down.
+ * Files with more blocks than hb_encode_many batches go through
+ * hb_encode(HB_PRF_CXX) inside the same call, so any mix of sizes is accepted.
+ * Every file is checked before any GPU work and hb_last_error names the
+ * rejected file's index ("file 3: ..."); what hb_encode(HB_PRF_CXX) rejects
+ * fails the whole call with that call's code -- a prime whose ByteCount is not
+ * a multiple of 16 with HB_EUNSUPPORTED -- and no tag buffer is written.
+ * flags: HB_DATA_ON_DEVICE and/or HB_TAGS_ON_DEVICE (device pointers of any
+ * alignment); anything else returns HB_EUNSUPPORTED.  nfiles == 0 returns
+ * HB_OK.  *tries_out (may be NULL) receives the sum of the files' F tries:
+ * what nfiles hb_encode calls report in total. */
+int hb_cxx_encode_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                       size_t key_len, const hb_file_desc *files, uint64_t nfiles,
+                       uint32_t flags, uint64_t *tries_out);
 
 /* The cxx prf, prf::evaluate(i) (cxx/prf.hxx:125-145), for n unsigned-int
  * inputs, keyed by key and bounded by limit (any limit up to 2048 bits; when
