@@ -536,6 +536,94 @@ class Swizzle(_Serializable):
                                                       len(vmax), mub, rhs))
         return int(proof.sigma) == int.from_bytes(rhs.raw, "big")
 
+    def prove_many(self, items):
+        """prove() of every (file, chal, tag) of `items` in one batched GPU
+        call (hb_cxx_prove_many): [Proof, ...], exactly what a loop of prove()
+        (:731-789) returns, in order -- a zero proof for chunks <= 0 -- and
+        HeartbeatError("tag is empty") at the first item a loop would raise it
+        for.  Every item is checked before any GPU work, so a failing item
+        costs no launch.  Files are read at absolute offsets and their
+        position is restored.  Items whose key length differs from the
+        batch's majority go through prove() one by one, and so do challenges
+        that prove() would shard over several GPUs and a batch of fewer than
+        CXX_PROVE_MANY_MIN items."""
+        items = list(items)
+        S = self.sectors
+        out = [None] * len(items)
+        cand = []
+        for i, (file, chal, tag) in enumerate(items):
+            self._check()
+            if len(tag) == 0:
+                raise HeartbeatError("tag is empty")
+            if int(chal.chunks) <= 0:
+                out[i] = Proof()
+                out[i].mu = [0] * S
+                out[i].sigma = 0
+            else:
+                cand.append(i)
+        ndev = len(multi.devices())
+        lens = [len(_kb(items[i][1].key)) for i in cand]
+        major = max(set(lens), key=lens.count) if lens else 0
+        batch = [i for i, kl in zip(cand, lens) if kl == major and
+                 multi.shard_count(ndev, int(items[i][1].chunks), multi.MIN_SHARD_CHUNKS) == 1]
+        if len(batch) < CXX_PROVE_MANY_MIN:
+            batch = []
+        if batch:
+            res = prove_files(self.prime, S, [(items[i][1].key, int(items[i][1].chunks), int(items[i][1].v_max),
+                                               items[i][2], items[i][0]) for i in batch])
+            for i, (mu, sigma) in zip(batch, res):
+                out[i] = Proof()
+                out[i].mu, out[i].sigma = mu, sigma
+        for i, (file, chal, tag) in enumerate(items):
+            if out[i] is None:
+                out[i] = self.prove(file, chal, tag)
+        return out
+
+    def verify_many(self, items):
+        """verify() of every (proof, chal, state) of `items` in one batched
+        GPU call (hb_cxx_verify_rhs_many): exactly what a loop of verify()
+        (:791-842) returns, in order -- None for arguments of the wrong types,
+        False for a state that does not authenticate or len(mu) != sectors --
+        and HeartbeatError("state has no chunks") as the loop would raise it.
+        Every item is checked before any GPU work, on a copy of its state.
+        Items whose key lengths differ from the batch's majority go through
+        verify() one by one, and so does a batch of fewer than
+        CXX_VERIFY_MANY_MIN items."""
+        items = list(items)
+        S = self.sectors
+        out = [None] * len(items)
+        pre = {}
+        for i, (proof, chal, state) in enumerate(items):
+            if not (isinstance(proof, Proof) and isinstance(chal, Challenge) and isinstance(state, State)):
+                continue   # None
+            s = state._copy()   # `state s = s_enc` (:796)
+            if s.encrypted and not s._check_sig_and_decrypt(self.k_enc, self.k_mac):
+                out[i] = False
+                continue
+            self._check()
+            mu = list(proof.mu)
+            if len(mu) != S:
+                out[i] = False
+                continue
+            chunks = max(int(chal.chunks), 0)
+            if chunks and int(s.n) <= 0:
+                raise HeartbeatError("state has no chunks")
+            pre[i] = (_kb(s.f_key), _kb(s.alpha_key), int(s.n), _kb(chal.key), chunks,
+                      int(chal.v_max) if chunks else 1, mu)
+        lens = [(len(t[0]), len(t[1]), len(t[3])) for t in pre.values()]
+        major = max(set(lens), key=lens.count) if lens else None
+        batch = [i for i, kl in zip(pre, lens) if kl == major and kl[0] == kl[1]]
+        if len(batch) < CXX_VERIFY_MANY_MIN:
+            batch = []
+        if batch:
+            rhs = verify_rhs_many(self.prime, S, [pre[i] for i in batch])
+            for i, r in zip(batch, rhs):
+                out[i] = int(items[i][0].sigma) == r
+        for i in pre:
+            if out[i] is None:
+                out[i] = self.verify(*items[i])
+        return out
+
     @staticmethod
     def tag_type():
         return Tag
@@ -621,6 +709,134 @@ def encode_files(p, sectors, keys, files):
         for fb in fbs:
             fb.close()
     return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+
+
+# Fewest proofs Swizzle.prove_many sends through hb_cxx_prove_many, and
+# Swizzle.verify_many through hb_cxx_verify_rhs_many; below them the items go
+# through prove() / verify() one by one.  Already one proof is ahead in the
+# batch (1024-bit, S = 10, a 1 MiB file, B's slowest round against A's fastest:
+# prove 1.37x device-resident and 1.26x from host memory at check_fraction 1.0,
+# 1.84x and 1.44x at 0.3; verify 1.43x and 1.62x; from 2.3x at two proofs and
+# 3.1x at three: the 1-, 2- and 3-proof rows of scripts/cxx_pv_many_rate.py,
+# profiles/many/cxx_pv_many_rate.json) -- the single cxx calls
+# take none of the fused paths: a prove is a PRF launch, a weighted sum and
+# their synchronisation, a verify up to four PRF launches, a Montgomery pass
+# and a sum -- so every non-empty list takes the batch.
+CXX_PROVE_MANY_MIN = 1
+CXX_VERIFY_MANY_MIN = 1
+
+
+def prove_files(p, sectors, items):
+    """Batched GPU prove (hb_cxx_prove_many) of many challenges with the cxx
+    prf: `items` is a list of (chal_key, chunks, v_max, tag, file) with a Tag
+    and a file object / buffer each; returns [(mu list, sigma), ...], what
+    hb_prove(HB_PRF_CXX) gives per item (shacham_waters_private.cxx:731-789).
+    Every file is read whole, from its start, and its position is left where
+    it was, as by Swizzle.prove.  Every item is checked before any GPU work.
+    All challenge keys of a batch have one length.  Runs on
+    multi.primary_context() (a batch is not spread over several GPUs)."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    if p.bit_length() // 8 < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if S < 1:
+        raise HeartbeatError("sectors must be positive")
+    keep = []
+    for ck, chunks, v_max, tag, file in items:
+        if len(tag) == 0:
+            raise HeartbeatError("tag is empty")
+        keep.append((_kb(ck), max(int(chunks), 0), _native.be(int(v_max)), tag, file))
+    if len({len(t[0]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    w = _native.width_of(p)
+    n = len(keep)
+    descs = (_native.ProveDesc * n)()
+    out = ctypes.create_string_buffer((S + 1) * w * n)
+    base = ctypes.addressof(out)
+    fbs, tarrs = [], []
+    try:
+        for i, (ck, chunks, vmax, tag, file) in enumerate(keep):
+            # absolute offsets from the start of the file, as the reference's
+            # f.seek(pos) before every read (shacham_waters_private.cxx:763-764)
+            fb = FileBuffer(file, from_start=True)
+            fbs.append(fb)
+            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
+            tarrs.append(tarr)
+            d = descs[i]
+            d.chal_key, d.chunks = ck, chunks
+            d.vmax_be, d.vmax_len = vmax, len(vmax)
+            d.tags, d.ntags = tarr.ctypes.data, len(tag)
+            d.data, d.len = fb.addr, fb.len
+            d.mu_out = base + i * (S + 1) * w
+            d.sigma_out = base + (i * (S + 1) + S) * w
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        with ctx.lock:
+            ctx.check(_native.lib().hb_cxx_prove_many(ctx.h, pb, len(pb), S, len(keep[0][0]), descs, n, 0))
+    finally:
+        for fb in fbs:
+            fb.restore()
+            fb.close()
+    raw = out.raw
+    res = []
+    for i in range(n):
+        vals = [int.from_bytes(raw[(i * (S + 1) + j) * w:(i * (S + 1) + j + 1) * w], "big") for j in range(S + 1)]
+        res.append((vals[:S], vals[S]))
+    return res
+
+
+def verify_rhs_many(p, sectors, items):
+    """Batched right-hand sides (hb_cxx_verify_rhs_many) of many proofs with
+    the cxx prf: `items` is a list of (f_key, alpha_key, state_chunks,
+    chal_key, chunks, v_max, mu_list) with decrypted state keys; returns the
+    list of ints that hb_cxx_verify_rhs gives per item
+    (shacham_waters_private.cxx:791-842).  Every item is checked before any
+    GPU work.  All f_keys and alpha_keys of a batch have one length, all
+    challenge keys one length.  Runs on multi.primary_context() (a batch is
+    not spread over several GPUs)."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    if p.bit_length() // 8 < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if S < 1:
+        raise HeartbeatError("sectors must be positive")
+    w = _native.width_of(p)
+    keep = []
+    for fk, ak, nstate, ck, chunks, v_max, mu in items:
+        mu = list(mu)
+        if len(mu) != S:
+            raise HeartbeatError("proof has %d mu values, not %d" % (len(mu), S))
+        chunks = max(int(chunks), 0)
+        keep.append((_kb(fk), _kb(ak), _kb(ck), int(nstate), chunks,
+                     _native.be(int(v_max)) if chunks else b"\x01",
+                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu)))
+    if len({len(t[0]) for t in keep} | {len(t[1]) for t in keep}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if len({len(t[2]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    descs = (_native.VerifyDesc * len(keep))()
+    out = ctypes.create_string_buffer(w * len(keep))
+    base = ctypes.addressof(out)
+    for i, (fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
+        d = descs[i]
+        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
+        d.state_chunks, d.chunks = nstate, chunks
+        d.vmax_be, d.vmax_len = vmax, len(vmax)
+        d.mu = mub
+        d.rhs_out = base + i * w
+    ctx = multi.primary_context()
+    pb = _native.be(p)
+    with ctx.lock:
+        ctx.check(_native.lib().hb_cxx_verify_rhs_many(ctx.h, pb, len(pb), S, len(keep[0][0]), len(keep[0][2]),
+                                                       descs, len(keep), 0))
+    raw = out.raw
+    return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
 
 
 # The extension module's path (cxx/Swizzle.hxx:738, imported as

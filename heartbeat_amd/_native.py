@@ -96,6 +96,10 @@ SIGNATURES = [
     ("hb_cxx_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                      _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                      _B, _P]),
+    ("hb_cxx_prove_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(ProveDesc),
+                                     _c.c_uint64, _c.c_uint32]),
+    ("hb_cxx_verify_rhs_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.c_size_t,
+                                          _c.POINTER(VerifyDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_aes_cfb8", _c.c_int, [_B, _c.c_size_t, _B, _B, _P, _c.c_size_t, _c.c_int]),
     ("hb_aes_cfb128", _c.c_int, [_B, _c.c_size_t, _B, _B, _P, _c.c_size_t, _c.c_int]),
     ("hb_last_kernel_ms", _c.c_int, [_P, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint32)]),

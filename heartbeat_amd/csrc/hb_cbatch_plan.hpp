@@ -1,4 +1,5 @@
-// hb_cbatch_plan.hpp -- the planner of the batched cxx calls (hb_cxx_encode_many):
+// hb_cbatch_plan.hpp -- the planner of the batched cxx calls (hb_cxx_encode_many,
+// hb_cxx_prove_many, hb_cxx_verify_rhs_many):
 // which items go through the batch path, how they fall into groups, where each
 // item's evaluations sit in its group, and the group's queue of wave-jobs.  A
 // pure host function: no HIP, no context, no allocation beyond its result, so
@@ -27,7 +28,11 @@ static_assert(HB_CB_JOB >= 64 && HB_CB_JOB % 64 == 0, "HB_CB_JOB is a multiple o
 // kinds of a wave-job (also its queue slot: tries)
 #define HB_CB_F 0u                // F(k) = cxx prf(f_key, p)(k), k < blocks
 #define HB_CB_ALPHA 1u            // alpha_j = cxx prf(alpha_key, p)(j), j < S
-#define HB_CB_KINDS 2u
+// the batched cxx prove and verify (hb_cpv.hpp); an encode item has none
+#define HB_CB_V 2u                // v_i = cxx prf(chal_key, v_max)(i), i < chunks
+#define HB_CB_IDX 3u              // idx_i = cxx prf(chal_key, ntags)(i): prove, sampled
+#define HB_CB_IDXF 4u             // F(idx_i), the index drawn in the same lane (check_all: F(i)): verify
+#define HB_CB_KINDS 5u
 
 // The device reads this table entry as four dwords (hb_load_uniform).
 struct HbCbJob {

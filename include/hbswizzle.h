@@ -129,7 +129,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
 #define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode */
-#define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many and hb_prove_many put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
+#define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many, hb_prove_many and their cxx counterparts put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
 uint32_t hb_test_switches(void);
 
 /* Number of visible HIP devices (multi-GPU sharding of encode / prove opens
@@ -459,6 +459,63 @@ int hb_cxx_verify_rhs(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t s
                       const uint8_t *chal_key, size_t chal_key_len, uint64_t chunks,
                       const uint8_t *vmax_be, size_t vmax_len,
                       const uint8_t *mu, uint8_t *rhs_out);
+
+/* hb_prove_many for the cxx Swizzle (heartbeat.Heartbeat): mu and sigma of
+ * many proofs, each under its own challenge key, file and tag array, in one
+ * call.  Replaces a storage node's loop over
+ * cxx/shacham_waters_private.cxx:731-789 with the prf of cxx/prf.hxx:125-176:
+ * proof i's mu_out and sigma_out receive exactly the bytes that hb_prove
+ * writes for the same arguments with flags | HB_PRF_CXX.  Same descriptors as
+ * hb_prove_many; one prime, one `sectors` and one key_len for the batch.
+ * The cxx semantics are the single call's: every block in order, without the
+ * index prf, when chunks >= ntags (check_all, :754-762; the default Swizzle
+ * audit); otherwise idx_i from the byte-granular prf on the limit ntags with
+ * the 81-try forced accept (prf.hxx:135-142); sector offsets in unsigned int
+ * (:738, 762-763).  An index that the forced accept leaves >= ntags (below
+ * 2^-81 per index) contributes zero and fails the call with HB_EINVAL
+ * "proof i: vector::_M_range_check..." as the single call does; no address is
+ * formed from it.  A try of the cxx prf is ByteCount(limit) / 16 full AES
+ * blocks, so the single call is bound by its launches and synchronisations:
+ * here a group of proofs is one copy up, one PRF launch (one lane per
+ * evaluation, wave-jobs of up to 64 evaluations of one proof under one key),
+ * one Montgomery pass over the group's v, one sum launch (a workgroup per
+ * proof and column) and one copy down.  Through hb_prove(HB_PRF_CXX) inside
+ * the same call, with identical results: every proof when ByteCount(p) is not
+ * a multiple of 16; a proof whose ByteCount(v_max) is not, with host data and
+ * device tags, with a host file above max(2 n C, 8 MiB) (n the effective chunk
+ * count, C = sectors * sector size), or that alone passes the group's scratch
+ * cap.  A batched host file and its host tags go up in the group's one copy.
+ * Every descriptor is checked before any GPU work, with hb_prove_many's rules
+ * and codes, and hb_last_error names the proof's index; ntags >= 2^32 returns
+ * HB_EUNSUPPORTED.  chunks == 0 gives zero mu and sigma.  nproofs == 0 returns
+ * HB_OK.  flags: HB_DATA_ON_DEVICE and/or HB_TAGS_ON_DEVICE; anything else
+ * returns HB_EUNSUPPORTED.  Parity unpinned (Crypto++ absent). */
+int hb_cxx_prove_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                      size_t key_len, const hb_prove_desc *proofs, uint64_t nproofs, uint32_t flags);
+
+/* hb_verify_rhs_many for the cxx Swizzle: the right-hand sides of many
+ * proofs, each under its own keys, in one call.  Replaces an auditor's loop
+ * over cxx/shacham_waters_private.cxx:791-842 with the prf of
+ * cxx/prf.hxx:125-176: proof i's rhs_out receives exactly the bytes that
+ * hb_cxx_verify_rhs writes for the same arguments.  Same descriptors as
+ * hb_verify_rhs_many.  check_all when chunks >= state_chunks (:822-827): F(i)
+ * of every block in order, v_i = prf(chal_key, v_max)(i), no index prf;
+ * otherwise the lane that evaluates F draws idx_i first (byte-granular prf on
+ * the limit state_chunks, forced accept after 81 tries) and F takes any index
+ * (verify has no range check).  A group of proofs is one copy up, one PRF
+ * launch (v, F and alpha of every proof), one sum launch (a workgroup per
+ * proof) and one copy down.  Through hb_cxx_verify_rhs inside the same call,
+ * with identical results: every proof when ByteCount(p) is not a multiple of
+ * 16 or key_len and chal_key_len have different AES round counts; a proof
+ * whose ByteCount(v_max) is not a multiple of 16 or that alone passes the
+ * group's scratch cap.  Every descriptor is checked before any GPU work, with
+ * hb_verify_rhs_many's rules and codes (state_chunks >= 2^32:
+ * HB_EUNSUPPORTED, as hb_cxx_verify_rhs), and hb_last_error names the proof's
+ * index.  chunks == 0 gives sum_j alpha_j mu_j.  nproofs == 0 returns HB_OK.
+ * flags must be 0.  Parity unpinned. */
+int hb_cxx_verify_rhs_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                           size_t key_len, size_t chal_key_len,
+                           const hb_verify_desc *proofs, uint64_t nproofs, uint32_t flags);
 
 /* Host AES-CFB8 (segment 8, any 16-byte IV) for PySwizzle State
  * encrypt/decrypt (PySwizzle.py:162-195): 64 bytes per call, not a hot path.
