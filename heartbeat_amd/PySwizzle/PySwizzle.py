@@ -27,7 +27,7 @@ import os
 
 import numpy as np
 
-from .. import _native, multi
+from .. import _many, _native, multi
 from .._filebuf import FileBuffer
 from ..exc import HeartbeatError
 from ..util import KeyedPRF, hb_decode, hb_encode
@@ -226,8 +226,7 @@ class State(object):
         self.hmac = self.get_hmac(key)
 
 
-def _kb(key):
-    return key.encode("latin-1") if isinstance(key, str) else bytes(key)
+_kb = _many._kb
 
 
 class Proof(object):
@@ -516,50 +515,8 @@ def encode_files(p, sectors, keys, files):
     Each file is read from its current position to EOF and left there, as by
     encode_file; all keys of a batch have one length.  Runs on
     multi.primary_context() (a batch is not spread over several GPUs)."""
-    p = int(p)
-    files = list(files)
-    keys = list(keys)
-    if len(keys) != len(files):
-        raise HeartbeatError("%d key pairs for %d files" % (len(keys), len(files)))
-    ss = p.bit_length() // 8
-    if ss < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if int(sectors) < 1:
-        raise HeartbeatError("sectors must be positive")
-    kb = [(_kb(fk), _kb(ak)) for fk, ak in keys]
-    if len({len(k) for pair in kb for k in pair}) > 1:
-        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
-    if not files:
-        return []
-    w = _native.width_of(p)
-    C = ss * int(sectors)
-    fbs, outs = [], []
-    try:
-        descs = (_native.FileDesc * len(files))()
-        for i, file in enumerate(files):
-            fb = FileBuffer(file)
-            fbs.append(fb)
-            nblocks = fb.len // C + 1
-            # the tags land in the array the Tag keeps
-            out = np.empty(nblocks * w, dtype=np.uint8)
-            outs.append((out, nblocks))
-            d = descs[i]
-            d.f_key, d.alpha_key = kb[i]
-            d.data = fb.addr
-            d.len = fb.len
-            d.tags = out.ctypes.data
-        ctx = multi.primary_context()
-        pb = _native.be(p)
-        tries = ctypes.c_uint64()
-        with ctx.lock:
-            ctx.check(_native.lib().hb_encode_many(ctx.h, pb, len(pb), int(sectors), len(kb[0][0]), descs,
-                                                   len(files), 0, ctypes.byref(tries)))
-        for fb in fbs:
-            fb.consume()
-    finally:
-        for fb in fbs:
-            fb.close()
-    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+    # a file is opened as its descriptor is filled
+    return _many.encode_files("hb_encode_many", Tag, p, sectors, keys, files, open_first=False)
 
 
 # Fewest proofs PySwizzle.prove_many sends through hb_prove_many; below it the
@@ -579,58 +536,7 @@ def prove_files(p, sectors, items):
     position is left where it was, as by PySwizzle.prove.  All challenge keys
     of a batch have one length.  Runs on multi.primary_context() (a batch is
     not spread over several GPUs)."""
-    p = int(p)
-    S = int(sectors)
-    items = list(items)
-    if p.bit_length() // 8 < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if S < 1:
-        raise HeartbeatError("sectors must be positive")
-    keep = []
-    for ck, chunks, v_max, tag, file in items:
-        if len(tag) == 0:
-            raise HeartbeatError("tag is empty")
-        chunks = max(int(chunks), 0)
-        keep.append((_kb(ck), chunks, _native.be(int(v_max)), tag, file))
-    if len({len(t[0]) for t in keep}) > 1:
-        raise HeartbeatError("all challenge keys of a batch must have the same length")
-    if not keep:
-        return []
-    w = _native.width_of(p)
-    n = len(keep)
-    descs = (_native.ProveDesc * n)()
-    out = ctypes.create_string_buffer((S + 1) * w * n)
-    base = ctypes.addressof(out)
-    fbs, tarrs = [], []
-    try:
-        for i, (ck, chunks, vmax, tag, file) in enumerate(keep):
-            # absolute offsets from the start of the file, as the reference's
-            # file.seek(pos) before every read (PySwizzle.py:353-355)
-            fb = FileBuffer(file, from_start=True)
-            fbs.append(fb)
-            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
-            tarrs.append(tarr)
-            d = descs[i]
-            d.chal_key, d.chunks = ck, chunks
-            d.vmax_be, d.vmax_len = vmax, len(vmax)
-            d.tags, d.ntags = tarr.ctypes.data, len(tag)
-            d.data, d.len = fb.addr, fb.len
-            d.mu_out = base + i * (S + 1) * w
-            d.sigma_out = base + (i * (S + 1) + S) * w
-        ctx = multi.primary_context()
-        pb = _native.be(p)
-        with ctx.lock:
-            ctx.check(_native.lib().hb_prove_many(ctx.h, pb, len(pb), S, len(keep[0][0]), descs, n, 0))
-    finally:
-        for fb in fbs:
-            fb.restore()
-            fb.close()
-    raw = out.raw
-    res = []
-    for i in range(n):
-        vals = [int.from_bytes(raw[(i * (S + 1) + j) * w:(i * (S + 1) + j + 1) * w], "big") for j in range(S + 1)]
-        res.append((vals[:S], vals[S]))
-    return res
+    return _many.prove_files("hb_prove_many", p, sectors, items)
 
 
 # Fewest proofs PySwizzle.verify_many sends through hb_verify_rhs_many; below
@@ -650,46 +556,8 @@ def verify_rhs_many(p, sectors, items):
     hb_verify_rhs gives per item (PySwizzle.py:381-394).  All f_keys and
     alpha_keys of a batch have one length, all challenge keys one length.  Runs
     on multi.primary_context() (a batch is not spread over several GPUs)."""
-    p = int(p)
-    S = int(sectors)
-    items = list(items)
-    if p.bit_length() // 8 < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if S < 1:
-        raise HeartbeatError("sectors must be positive")
-    w = _native.width_of(p)
-    keep = []
-    for fk, ak, nstate, ck, chunks, v_max, mu in items:
-        mu = list(mu)
-        if len(mu) < S:
-            raise HeartbeatError("proof has fewer than %d mu values" % S)
-        chunks = max(int(chunks), 0)
-        keep.append((_kb(fk), _kb(ak), _kb(ck), int(nstate), chunks,
-                     _native.be(int(v_max)) if chunks > 0 else b"\x01",
-                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu[:S])))
-    if len({len(t[0]) for t in keep} | {len(t[1]) for t in keep}) > 1:
-        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
-    if len({len(t[2]) for t in keep}) > 1:
-        raise HeartbeatError("all challenge keys of a batch must have the same length")
-    if not keep:
-        return []
-    descs = (_native.VerifyDesc * len(keep))()
-    out = ctypes.create_string_buffer(w * len(keep))
-    base = ctypes.addressof(out)
-    for i, (fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
-        d = descs[i]
-        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
-        d.state_chunks, d.chunks = nstate, chunks
-        d.vmax_be, d.vmax_len = vmax, len(vmax)
-        d.mu = mub
-        d.rhs_out = base + i * w
-    ctx = multi.primary_context()
-    pb = _native.be(p)
-    with ctx.lock:
-        ctx.check(_native.lib().hb_verify_rhs_many(ctx.h, pb, len(pb), S, len(keep[0][0]), len(keep[0][2]),
-                                                   descs, len(keep), 0))
-    raw = out.raw
-    return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
+    # more than `sectors` mu values are accepted: the first `sectors` count
+    return _many.verify_rhs_many("hb_verify_rhs_many", p, sectors, items, exact_mu=False)
 
 
 # The reference's module path (heartbeat/PySwizzle/PySwizzle.py): pickles of

@@ -36,7 +36,7 @@ import struct
 
 import numpy as np
 
-from . import _native, multi
+from . import _many, _native, multi
 from ._filebuf import FileBuffer
 from .exc import HeartbeatError
 from .PySwizzle.PySwizzle import _kb, _random_bytes, getPrime
@@ -661,54 +661,7 @@ def encode_files(p, sectors, keys, files):
     before it are left at EOF as the loop leaves them and its error is raised.
     Runs on multi.primary_context() (a batch is not spread over several
     GPUs)."""
-    p = int(p)
-    files = list(files)
-    keys = list(keys)
-    if len(keys) != len(files):
-        raise HeartbeatError("%d key pairs for %d files" % (len(keys), len(files)))
-    ss = p.bit_length() // 8
-    if ss < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if int(sectors) < 1:
-        raise HeartbeatError("sectors must be positive")
-    kb = [(_kb(fk), _kb(ak)) for fk, ak in keys]
-    if len({len(k) for pair in kb for k in pair}) > 1:
-        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
-    if not files:
-        return []
-    w = _native.width_of(p)
-    C = ss * int(sectors)
-    fbs, outs = [], []
-    try:
-        descs = (_native.FileDesc * len(files))()
-        try:
-            for file in files:
-                fbs.append(FileBuffer(file))
-        except BaseException:
-            for fb in fbs:
-                fb.consume()
-            raise
-        for d, fb, (fk, ak) in zip(descs, fbs, kb):
-            nblocks = fb.len // C + 1
-            # the tags land in the array the Tag keeps
-            out = np.empty(nblocks * w, dtype=np.uint8)
-            outs.append((out, nblocks))
-            d.f_key, d.alpha_key = fk, ak
-            d.data = fb.addr
-            d.len = fb.len
-            d.tags = out.ctypes.data
-        ctx = multi.primary_context()
-        pb = _native.be(p)
-        tries = ctypes.c_uint64()
-        with ctx.lock:
-            ctx.check(_native.lib().hb_cxx_encode_many(ctx.h, pb, len(pb), int(sectors), len(kb[0][0]), descs,
-                                                       len(files), 0, ctypes.byref(tries)))
-        for fb in fbs:
-            fb.consume()
-    finally:
-        for fb in fbs:
-            fb.close()
-    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+    return _many.encode_files("hb_cxx_encode_many", Tag, p, sectors, keys, files, open_first=True)
 
 
 # Fewest proofs Swizzle.prove_many sends through hb_cxx_prove_many, and
@@ -735,57 +688,7 @@ def prove_files(p, sectors, items):
     it was, as by Swizzle.prove.  Every item is checked before any GPU work.
     All challenge keys of a batch have one length.  Runs on
     multi.primary_context() (a batch is not spread over several GPUs)."""
-    p = int(p)
-    S = int(sectors)
-    items = list(items)
-    if p.bit_length() // 8 < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if S < 1:
-        raise HeartbeatError("sectors must be positive")
-    keep = []
-    for ck, chunks, v_max, tag, file in items:
-        if len(tag) == 0:
-            raise HeartbeatError("tag is empty")
-        keep.append((_kb(ck), max(int(chunks), 0), _native.be(int(v_max)), tag, file))
-    if len({len(t[0]) for t in keep}) > 1:
-        raise HeartbeatError("all challenge keys of a batch must have the same length")
-    if not keep:
-        return []
-    w = _native.width_of(p)
-    n = len(keep)
-    descs = (_native.ProveDesc * n)()
-    out = ctypes.create_string_buffer((S + 1) * w * n)
-    base = ctypes.addressof(out)
-    fbs, tarrs = [], []
-    try:
-        for i, (ck, chunks, vmax, tag, file) in enumerate(keep):
-            # absolute offsets from the start of the file, as the reference's
-            # f.seek(pos) before every read (shacham_waters_private.cxx:763-764)
-            fb = FileBuffer(file, from_start=True)
-            fbs.append(fb)
-            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
-            tarrs.append(tarr)
-            d = descs[i]
-            d.chal_key, d.chunks = ck, chunks
-            d.vmax_be, d.vmax_len = vmax, len(vmax)
-            d.tags, d.ntags = tarr.ctypes.data, len(tag)
-            d.data, d.len = fb.addr, fb.len
-            d.mu_out = base + i * (S + 1) * w
-            d.sigma_out = base + (i * (S + 1) + S) * w
-        ctx = multi.primary_context()
-        pb = _native.be(p)
-        with ctx.lock:
-            ctx.check(_native.lib().hb_cxx_prove_many(ctx.h, pb, len(pb), S, len(keep[0][0]), descs, n, 0))
-    finally:
-        for fb in fbs:
-            fb.restore()
-            fb.close()
-    raw = out.raw
-    res = []
-    for i in range(n):
-        vals = [int.from_bytes(raw[(i * (S + 1) + j) * w:(i * (S + 1) + j + 1) * w], "big") for j in range(S + 1)]
-        res.append((vals[:S], vals[S]))
-    return res
+    return _many.prove_files("hb_cxx_prove_many", p, sectors, items)
 
 
 def verify_rhs_many(p, sectors, items):
@@ -797,46 +700,8 @@ def verify_rhs_many(p, sectors, items):
     GPU work.  All f_keys and alpha_keys of a batch have one length, all
     challenge keys one length.  Runs on multi.primary_context() (a batch is
     not spread over several GPUs)."""
-    p = int(p)
-    S = int(sectors)
-    items = list(items)
-    if p.bit_length() // 8 < 1:
-        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
-    if S < 1:
-        raise HeartbeatError("sectors must be positive")
-    w = _native.width_of(p)
-    keep = []
-    for fk, ak, nstate, ck, chunks, v_max, mu in items:
-        mu = list(mu)
-        if len(mu) != S:
-            raise HeartbeatError("proof has %d mu values, not %d" % (len(mu), S))
-        chunks = max(int(chunks), 0)
-        keep.append((_kb(fk), _kb(ak), _kb(ck), int(nstate), chunks,
-                     _native.be(int(v_max)) if chunks else b"\x01",
-                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu)))
-    if len({len(t[0]) for t in keep} | {len(t[1]) for t in keep}) > 1:
-        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
-    if len({len(t[2]) for t in keep}) > 1:
-        raise HeartbeatError("all challenge keys of a batch must have the same length")
-    if not keep:
-        return []
-    descs = (_native.VerifyDesc * len(keep))()
-    out = ctypes.create_string_buffer(w * len(keep))
-    base = ctypes.addressof(out)
-    for i, (fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
-        d = descs[i]
-        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
-        d.state_chunks, d.chunks = nstate, chunks
-        d.vmax_be, d.vmax_len = vmax, len(vmax)
-        d.mu = mub
-        d.rhs_out = base + i * w
-    ctx = multi.primary_context()
-    pb = _native.be(p)
-    with ctx.lock:
-        ctx.check(_native.lib().hb_cxx_verify_rhs_many(ctx.h, pb, len(pb), S, len(keep[0][0]), len(keep[0][2]),
-                                                       descs, len(keep), 0))
-    raw = out.raw
-    return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
+    # exactly `sectors` mu values, as the message says
+    return _many.verify_rhs_many("hb_cxx_verify_rhs_many", p, sectors, items, exact_mu=True)
 
 
 # The extension module's path (cxx/Swizzle.hxx:738, imported as

@@ -1,0 +1,181 @@
+"""The Python side of the batched calls, once: descriptors in, results out.
+PySwizzle.py (hb_encode_many, hb_prove_many, hb_verify_rhs_many) and Swizzle.py
+(their hb_cxx_* twins) wrap these under their public names; `native` is the
+entry point's name in libhbswizzle.so, `Tag` the caller's tag class."""
+import ctypes
+
+import numpy as np
+
+from . import _native, multi
+from ._filebuf import FileBuffer
+from .exc import HeartbeatError
+
+
+def _kb(key):
+    return key.encode("latin-1") if isinstance(key, str) else bytes(key)
+
+
+def _check(p, sectors):
+    if p.bit_length() // 8 < 1:
+        raise HeartbeatError("prime must be at least 2^8 (sector size of at least one byte)")
+    if sectors < 1:
+        raise HeartbeatError("sectors must be positive")
+
+
+def encode_files(native, Tag, p, sectors, keys, files, open_first):
+    """[(Tag, number of blocks), ...] of `files` under keys[i] = (f_key,
+    alpha_key).  open_first (Swizzle.encode_files): every file is opened
+    before anything else is done, and if one cannot be read, the files before
+    it are consumed (left at EOF as the loop leaves them).  Without it
+    (PySwizzle.encode_files) a file is opened as its descriptor is filled and
+    a failure leaves the earlier files where they were."""
+    p = int(p)
+    sectors = int(sectors)
+    files = list(files)
+    keys = list(keys)
+    if len(keys) != len(files):
+        raise HeartbeatError("%d key pairs for %d files" % (len(keys), len(files)))
+    _check(p, sectors)
+    kb = [(_kb(fk), _kb(ak)) for fk, ak in keys]
+    if len({len(k) for pair in kb for k in pair}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if not files:
+        return []
+    w = _native.width_of(p)
+    C = (p.bit_length() // 8) * sectors
+    fbs, outs = [], []
+    try:
+        descs = (_native.FileDesc * len(files))()
+        if open_first:
+            try:
+                for file in files:
+                    fbs.append(FileBuffer(file))
+            except BaseException:
+                for fb in fbs:
+                    fb.consume()
+                raise
+        for i, (d, (fk, ak)) in enumerate(zip(descs, kb)):
+            if not open_first:
+                fbs.append(FileBuffer(files[i]))
+            fb = fbs[i]
+            nblocks = fb.len // C + 1
+            # the tags land in the array the Tag keeps
+            out = np.empty(nblocks * w, dtype=np.uint8)
+            outs.append((out, nblocks))
+            d.f_key, d.alpha_key = fk, ak
+            d.data = fb.addr
+            d.len = fb.len
+            d.tags = out.ctypes.data
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        tries = ctypes.c_uint64()
+        with ctx.lock:
+            ctx.check(getattr(_native.lib(), native)(ctx.h, pb, len(pb), sectors, len(kb[0][0]), descs, len(files), 0,
+                                                     ctypes.byref(tries)))
+        for fb in fbs:
+            fb.consume()
+    finally:
+        for fb in fbs:
+            fb.close()
+    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
+
+
+def prove_files(native, p, sectors, items):
+    """[(mu list, sigma), ...] of `items` = (chal_key, chunks, v_max, tag,
+    file).  Every file is read whole, from its start (absolute offsets, as the
+    references' seek(pos) before every read: PySwizzle.py:353-355,
+    shacham_waters_private.cxx:763-764), and its position is left where it
+    was."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    _check(p, S)
+    keep = []
+    for ck, chunks, v_max, tag, file in items:
+        if len(tag) == 0:
+            raise HeartbeatError("tag is empty")
+        keep.append((_kb(ck), max(int(chunks), 0), _native.be(int(v_max)), tag, file))
+    if len({len(t[0]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    w = _native.width_of(p)
+    n = len(keep)
+    descs = (_native.ProveDesc * n)()
+    out = ctypes.create_string_buffer((S + 1) * w * n)
+    base = ctypes.addressof(out)
+    fbs, tarrs = [], []
+    try:
+        for i, (ck, chunks, vmax, tag, file) in enumerate(keep):
+            fb = FileBuffer(file, from_start=True)
+            fbs.append(fb)
+            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
+            tarrs.append(tarr)
+            d = descs[i]
+            d.chal_key, d.chunks = ck, chunks
+            d.vmax_be, d.vmax_len = vmax, len(vmax)
+            d.tags, d.ntags = tarr.ctypes.data, len(tag)
+            d.data, d.len = fb.addr, fb.len
+            d.mu_out = base + i * (S + 1) * w
+            d.sigma_out = base + (i * (S + 1) + S) * w
+        ctx = multi.primary_context()
+        pb = _native.be(p)
+        with ctx.lock:
+            ctx.check(getattr(_native.lib(), native)(ctx.h, pb, len(pb), S, len(keep[0][0]), descs, n, 0))
+    finally:
+        for fb in fbs:
+            fb.restore()
+            fb.close()
+    raw = out.raw
+    res = []
+    for i in range(n):
+        vals = [int.from_bytes(raw[(i * (S + 1) + j) * w:(i * (S + 1) + j + 1) * w], "big") for j in range(S + 1)]
+        res.append((vals[:S], vals[S]))
+    return res
+
+
+def verify_rhs_many(native, p, sectors, items, exact_mu):
+    """The right-hand sides (ints) of `items` = (f_key, alpha_key,
+    state_chunks, chal_key, chunks, v_max, mu_list) with decrypted state keys.
+    exact_mu (Swizzle.verify_rhs_many): a proof has exactly `sectors` mu
+    values.  Without it (PySwizzle.verify_rhs_many) it may have more, and the
+    first `sectors` count."""
+    p = int(p)
+    S = int(sectors)
+    items = list(items)
+    _check(p, S)
+    w = _native.width_of(p)
+    keep = []
+    for fk, ak, nstate, ck, chunks, v_max, mu in items:
+        mu = list(mu)
+        if exact_mu and len(mu) != S:
+            raise HeartbeatError("proof has %d mu values, not %d" % (len(mu), S))
+        if len(mu) < S:
+            raise HeartbeatError("proof has fewer than %d mu values" % S)
+        chunks = max(int(chunks), 0)
+        keep.append((_kb(fk), _kb(ak), _kb(ck), int(nstate), chunks,
+                     _native.be(int(v_max)) if chunks > 0 else b"\x01",
+                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu[:S])))
+    if len({len(t[0]) for t in keep} | {len(t[1]) for t in keep}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if len({len(t[2]) for t in keep}) > 1:
+        raise HeartbeatError("all challenge keys of a batch must have the same length")
+    if not keep:
+        return []
+    descs = (_native.VerifyDesc * len(keep))()
+    out = ctypes.create_string_buffer(w * len(keep))
+    base = ctypes.addressof(out)
+    for i, (fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
+        d = descs[i]
+        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
+        d.state_chunks, d.chunks = nstate, chunks
+        d.vmax_be, d.vmax_len = vmax, len(vmax)
+        d.mu = mub
+        d.rhs_out = base + i * w
+    ctx = multi.primary_context()
+    pb = _native.be(p)
+    with ctx.lock:
+        ctx.check(getattr(_native.lib(), native)(ctx.h, pb, len(pb), S, len(keep[0][0]), len(keep[0][2]), descs,
+                                                 len(keep), 0))
+    raw = out.raw
+    return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]

@@ -1,8 +1,9 @@
-// hb_cbatch_plan.hpp -- the planner of the batched cxx calls (hb_cxx_encode_many,
-// hb_cxx_prove_many, hb_cxx_verify_rhs_many):
-// which items go through the batch path, how they fall into groups, where each
-// item's evaluations sit in its group, and the group's queue of wave-jobs.  A
-// pure host function: no HIP, no context, no allocation beyond its result, so
+// hb_cbatch_plan.hpp -- the planner of the batched calls: which items go
+// through the batch path, how they fall into groups and where each item's
+// evaluations sit in its group (hb_batch_groups: all six hb_*_many calls), and
+// a group's queue of wave-jobs (hb_cbatch_jobs: hb_cxx_encode_many,
+// hb_cxx_prove_many, hb_cxx_verify_rhs_many; hb_cbatch_plan is both).  Pure
+// host functions: no HIP, no context, no allocation beyond their result, so
 // that a stand-alone program can walk it (tests/cbatch/plan_main.cpp, built
 // with AddressSanitizer and UBSan).
 //
@@ -62,17 +63,19 @@ struct HbCbPlan {
     std::vector<HbCbJob> jobs;
 };
 
+// Which items the batch path takes and how they fall into groups: every batched
+// call's first question (the wave-job queue below is the cxx calls' second).
 // unit_bound: items with more units fall through.  cap_units / cap_bytes: a
 // group ends before the item that would take it over either (an item alone
-// may exceed them: every batched item gets a group).  An item without any
-// evaluation still belongs to a group (its outputs may need writing) but gets
-// no wave-job.
-inline HbCbPlan hb_cbatch_plan(const HbCbItemReq *items, uint64_t nitems, uint64_t unit_bound, uint64_t cap_units,
-                               uint64_t cap_bytes) {
+// may exceed them: every batched item gets a group).  The callers pass
+// unit_bound <= cap_units.  The result has no wave-jobs yet (jobs empty, every
+// group's job0 = njobs = 0).
+inline HbCbPlan hb_batch_groups(const HbCbItemReq *items, uint64_t nitems, uint64_t unit_bound, uint64_t cap_units,
+                                uint64_t cap_bytes) {
     HbCbPlan P;
     uint64_t i = 0;
     while (i < nitems) {
-        HbCbGroup G = {P.order.size(), 0, P.jobs.size(), 0, 0, 0};
+        HbCbGroup G = {P.order.size(), 0, 0, 0, 0, 0};
         for (; i < nitems; ++i) {
             const HbCbItemReq &R = items[i];
             if (R.units > unit_bound) {
@@ -84,25 +87,44 @@ inline HbCbPlan hb_cbatch_plan(const HbCbItemReq *items, uint64_t nitems, uint64
                 break;
             P.order.push_back(i);
             P.ubase.push_back(G.units);
-            for (uint32_t k = 0; k < HB_CB_KINDS; ++k)
-                for (uint64_t a = 0; a < R.n[k]; a += HB_CB_JOB) {
-                    const uint64_t left = R.n[k] - a;
-                    P.jobs.push_back(HbCbJob{(uint32_t)G.nitems, k, (uint32_t)a, (uint32_t)(left < HB_CB_JOB ? left : HB_CB_JOB)});
-                }
             ++G.nitems;
             G.units += R.units;
             G.bytes += R.bytes;
         }
         if (!G.nitems) break;
+        P.groups.push_back(G);
+    }
+    return P;
+}
+
+// The cxx calls' wave-job queues: HB_CB_JOB evaluations of one item and kind
+// each, per group longest first.  An item without any evaluation still belongs
+// to its group (its outputs may need writing) but gets no wave-job.
+inline void hb_cbatch_jobs(const HbCbItemReq *items, HbCbPlan &P) {
+    for (HbCbGroup &G : P.groups) {
+        G.job0 = P.jobs.size();
+        const uint64_t *ord = P.order.data() + G.item0;
+        for (uint64_t f = 0; f < G.nitems; ++f) {
+            const HbCbItemReq &R = items[ord[f]];
+            for (uint32_t k = 0; k < HB_CB_KINDS; ++k)
+                for (uint64_t a = 0; a < R.n[k]; a += HB_CB_JOB) {
+                    const uint64_t left = R.n[k] - a;
+                    P.jobs.push_back(HbCbJob{(uint32_t)f, k, (uint32_t)a, (uint32_t)(left < HB_CB_JOB ? left : HB_CB_JOB)});
+                }
+        }
         G.njobs = P.jobs.size() - G.job0;
         // longest wave-job first: a try's AES blocks, then the fuller wave-job
         // (its wave lasts as long as the longest of `count` rejection chains)
-        const uint64_t *ord = P.order.data() + G.item0;
         std::stable_sort(P.jobs.begin() + (ptrdiff_t)G.job0, P.jobs.end(), [&](const HbCbJob &a, const HbCbJob &b) {
             const uint32_t la = items[ord[a.item]].aes[a.kind], lb = items[ord[b.item]].aes[b.kind];
             return la != lb ? la > lb : a.count > b.count;
         });
-        P.groups.push_back(G);
     }
+}
+
+inline HbCbPlan hb_cbatch_plan(const HbCbItemReq *items, uint64_t nitems, uint64_t unit_bound, uint64_t cap_units,
+                               uint64_t cap_bytes) {
+    HbCbPlan P = hb_batch_groups(items, nitems, unit_bound, cap_units, cap_bytes);
+    hb_cbatch_jobs(items, P);
     return P;
 }
