@@ -15,6 +15,7 @@ Same class names, constructor arguments, method signatures, defaults,
         prove(file, chal, tag) -> Proof           PySwizzle.py:333-370
         verify(proof, chal, state) -> bool        PySwizzle.py:372-395
         verify_many(items) -> [bool]              a loop over :372-395, one GPU call
+        prove_mixed(items) / verify_mixed(items)  (static) the same for any mix of beats
 
 Tags produced by encode keep their fixed-width big-endian image (``Tag.raw``)
 so prove can hand them to the GPU without converting 2^27 Python ints; the
@@ -444,6 +445,87 @@ class PySwizzle(object):
         for i, (proof, chal, state) in enumerate(items):
             if out[i] is None:
                 out[i] = self.verify(proof, chal, state)
+        return out
+
+    @staticmethod
+    def prove_mixed(items):
+        """b.prove(file, chal, tag) of every (beat, file, chal, tag) of
+        `items`, with any mix of beats -- primes, sector counts, challenge key
+        lengths -- in one batched GPU call (hb_prove_mixed): the proofs a
+        storage node owes to many owners, each of whom drew their own prime
+        (PySwizzle.py:250-251).  [Proof, ...], exactly what
+        [b.prove(f, c, t) for b, f, c, t in items] returns (PySwizzle.py:333-370
+        per item) -- a zero proof for chunks <= 0 -- and the same
+        HeartbeatError at the first item a loop would raise it for.  Every
+        item is checked before any GPU work.  Challenges that prove() would
+        shard over several GPUs go through prove(), and so does a batch of
+        fewer than PROVE_MANY_MIN items."""
+        items = list(items)
+        out = [None] * len(items)
+        cand = []
+        for i, (beat, file, chal, tag) in enumerate(items):
+            beat._check()
+            if int(chal.chunks) <= 0:
+                out[i] = Proof()
+                out[i].mu = [0] * int(beat.sectors)
+                out[i].sigma = 0
+            elif len(tag) == 0:
+                raise HeartbeatError("tag is empty")
+            else:
+                cand.append(i)
+        ndev = len(multi.devices())
+        batch = [i for i in cand
+                 if multi.shard_count(ndev, int(items[i][2].chunks), multi.MIN_SHARD_CHUNKS) == 1]
+        if len(batch) < PROVE_MANY_MIN:
+            batch = []
+        if batch:
+            res = _many.prove_files_mixed(
+                [(int(items[i][0].prime), int(items[i][0].sectors), items[i][2].key, int(items[i][2].chunks),
+                  int(items[i][2].v_max), items[i][3], items[i][1]) for i in batch])
+            for i, (mu, sigma) in zip(batch, res):
+                out[i] = Proof()
+                out[i].mu, out[i].sigma = mu, sigma
+        for i, (beat, file, chal, tag) in enumerate(items):
+            if out[i] is None:
+                out[i] = beat.prove(file, chal, tag)
+        return out
+
+    @staticmethod
+    def verify_mixed(items):
+        """b.verify(proof, chal, state) of every (beat, proof, chal, state) of
+        `items`, with any mix of beats, in one batched GPU call
+        (hb_verify_rhs_mixed): an auditor checking the proofs of several
+        owners.  Each state is decrypted with its own beat's key.  [bool, ...],
+        exactly what a loop of verify() (PySwizzle.py:372-395) returns, and
+        the same HeartbeatError at the first item a loop would raise it for
+        (bad signature, too few mu values, a state without chunks).  Every
+        item is checked before any GPU work.  A batch of fewer than
+        VERIFY_MANY_MIN items goes through verify()."""
+        items = list(items)
+        pre = []
+        for beat, proof, chal, state in items:
+            state.decrypt(beat.key)
+            beat._check()
+            S = int(beat.sectors)
+            chunks = int(chal.chunks)
+            if chunks > 0 and int(state.chunks) <= 0:
+                raise HeartbeatError("state has no chunks")
+            mu = list(proof.mu)
+            if len(mu) < S:
+                raise HeartbeatError("proof has fewer than %d mu values" % S)
+            pre.append((int(beat.prime), S, _kb(state.f_key), _kb(state.alpha_key), int(state.chunks), _kb(chal.key),
+                        max(chunks, 0), int(chal.v_max) if chunks > 0 else 1, mu[:S]))
+        batch = [i for i, t in enumerate(pre) if len(t[2]) == len(t[3])]
+        if len(batch) < VERIFY_MANY_MIN:
+            batch = []
+        out = [None] * len(items)
+        if batch:
+            rhs = _many.verify_rhs_mixed([pre[i] for i in batch])
+            for i, r in zip(batch, rhs):
+                out[i] = items[i][1].sigma == r
+        for i, (beat, proof, chal, state) in enumerate(items):
+            if out[i] is None:
+                out[i] = beat.verify(proof, chal, state)
         return out
 
     @staticmethod

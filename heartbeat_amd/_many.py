@@ -179,3 +179,104 @@ def verify_rhs_many(native, p, sectors, items, exact_mu):
                                                  len(keep), 0))
     raw = out.raw
     return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
+
+
+def prove_files_mixed(items):
+    """[(mu list, sigma), ...] of `items` = (p, sectors, chal_key, chunks,
+    v_max, tag, file) in one hb_prove_mixed call: every item under its own
+    prime, sector count and key length (the proofs of many owners).  File
+    handling as prove_files: every file read whole from its start, its
+    position left where it was."""
+    keep = []
+    for p, S, ck, chunks, v_max, tag, file in items:
+        p, S = int(p), int(S)
+        _check(p, S)
+        if len(tag) == 0:
+            raise HeartbeatError("tag is empty")
+        keep.append((p, S, _native.be(p), _kb(ck), max(int(chunks), 0), _native.be(int(v_max)), tag, file))
+    if not keep:
+        return []
+    n = len(keep)
+    descs = (_native.ProveMixedDesc * n)()
+    offs, total = [], 0
+    for p, S, _, _, _, _, _, _ in keep:
+        offs.append(total)
+        total += (S + 1) * _native.width_of(p)
+    out = ctypes.create_string_buffer(max(total, 1))
+    base = ctypes.addressof(out)
+    fbs, tarrs = [], []
+    try:
+        for i, (p, S, pb, ck, chunks, vmax, tag, file) in enumerate(keep):
+            w = _native.width_of(p)
+            fb = FileBuffer(file, from_start=True)
+            fbs.append(fb)
+            tarr = np.frombuffer(tag.raw(p), dtype=np.uint8)
+            tarrs.append(tarr)
+            d = descs[i]
+            d.p_be, d.p_len, d.sectors, d.key_len = pb, len(pb), S, len(ck)
+            d.chal_key, d.chunks = ck, chunks
+            d.vmax_be, d.vmax_len = vmax, len(vmax)
+            d.tags, d.ntags = tarr.ctypes.data, len(tag)
+            d.data, d.len = fb.addr, fb.len
+            d.mu_out = base + offs[i]
+            d.sigma_out = base + offs[i] + S * w
+        ctx = multi.primary_context()
+        with ctx.lock:
+            ctx.check(_native.lib().hb_prove_mixed(ctx.h, descs, n, 0))
+    finally:
+        for fb in fbs:
+            fb.restore()
+            fb.close()
+    raw = out.raw
+    res = []
+    for i, (p, S, _, _, _, _, _, _) in enumerate(keep):
+        w = _native.width_of(p)
+        vals = [int.from_bytes(raw[offs[i] + j * w:offs[i] + (j + 1) * w], "big") for j in range(S + 1)]
+        res.append((vals[:S], vals[S]))
+    return res
+
+
+def verify_rhs_mixed(items):
+    """The right-hand sides (ints) of `items` = (p, sectors, f_key, alpha_key,
+    state_chunks, chal_key, chunks, v_max, mu_list) with decrypted state keys
+    in one hb_verify_rhs_mixed call: every item under its own prime, sector
+    count and key lengths.  A proof may have more than `sectors` mu values;
+    the first `sectors` count."""
+    keep = []
+    for p, S, fk, ak, nstate, ck, chunks, v_max, mu in items:
+        p, S = int(p), int(S)
+        _check(p, S)
+        w = _native.width_of(p)
+        mu = list(mu)
+        if len(mu) < S:
+            raise HeartbeatError("proof has fewer than %d mu values" % S)
+        fk, ak = _kb(fk), _kb(ak)
+        if len(fk) != len(ak):
+            raise HeartbeatError("f_key and alpha_key must have the same length")
+        chunks = max(int(chunks), 0)
+        keep.append((p, S, _native.be(p), fk, ak, _kb(ck), int(nstate), chunks,
+                     _native.be(int(v_max)) if chunks > 0 else b"\x01",
+                     b"".join((int(m) % p).to_bytes(w, "big") for m in mu[:S])))
+    if not keep:
+        return []
+    n = len(keep)
+    descs = (_native.VerifyMixedDesc * n)()
+    offs, total = [], 0
+    for t in keep:
+        offs.append(total)
+        total += _native.width_of(t[0])
+    out = ctypes.create_string_buffer(max(total, 1))
+    base = ctypes.addressof(out)
+    for i, (p, S, pb, fk, ak, ck, nstate, chunks, vmax, mub) in enumerate(keep):
+        d = descs[i]
+        d.p_be, d.p_len, d.sectors, d.key_len, d.chal_key_len = pb, len(pb), S, len(fk), len(ck)
+        d.f_key, d.alpha_key, d.chal_key = fk, ak, ck
+        d.state_chunks, d.chunks = nstate, chunks
+        d.vmax_be, d.vmax_len = vmax, len(vmax)
+        d.mu = mub
+        d.rhs_out = base + offs[i]
+    ctx = multi.primary_context()
+    with ctx.lock:
+        ctx.check(_native.lib().hb_verify_rhs_mixed(ctx.h, descs, n, 0))
+    raw = out.raw
+    return [int.from_bytes(raw[offs[i]:offs[i] + _native.width_of(keep[i][0])], "big") for i in range(n)]

@@ -59,6 +59,20 @@ class ProveDesc(ctypes.Structure):
                 ("mu_out", ctypes.c_void_p), ("sigma_out", ctypes.c_void_p)]
 
 
+class ProveMixedDesc(ctypes.Structure):
+    """hb_prove_mixed_desc (hbswizzle.h): one proof of an hb_prove_mixed call,
+    under its own prime, sector count and key length; then hb_prove_desc's words."""
+    _fields_ = [("p_be", ctypes.c_char_p), ("p_len", ctypes.c_uint64),
+                ("sectors", ctypes.c_uint64), ("key_len", ctypes.c_uint64)] + ProveDesc._fields_
+
+
+class VerifyMixedDesc(ctypes.Structure):
+    """hb_verify_mixed_desc (hbswizzle.h): one proof of an hb_verify_rhs_mixed
+    call, under its own prime, sector count and key lengths; then hb_verify_desc's words."""
+    _fields_ = [("p_be", ctypes.c_char_p), ("p_len", ctypes.c_uint64), ("sectors", ctypes.c_uint64),
+                ("key_len", ctypes.c_uint64), ("chal_key_len", ctypes.c_uint64)] + VerifyDesc._fields_
+
+
 SIGNATURES = [
     ("hb_abi_version", _c.c_int, []),
     ("hb_build_flags", _c.c_int, []),
@@ -88,6 +102,8 @@ SIGNATURES = [
                                   _c.c_uint64, _c.c_uint32, _P, _P]),
     ("hb_prove_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(ProveDesc),
                                  _c.c_uint64, _c.c_uint32]),
+    ("hb_prove_mixed", _c.c_int, [_P, _c.POINTER(ProveMixedDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_verify_rhs_mixed", _c.c_int, [_P, _c.POINTER(VerifyMixedDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                  _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                  _B, _P]),

@@ -31,8 +31,10 @@
 #include "hb_pbatch_args.hpp"
 #include "hb_cbatch_args.hpp"
 #include "hb_cpv_args.hpp"
+#include "hb_mixed_args.hpp"
 #include "hb_bignum_host.hpp"
 #include "hb_batch_host.hpp"
+#include "hb_mixed_host.hpp"
 
 using namespace hbhost;
 
@@ -67,6 +69,11 @@ template <int NL> hipError_t hb_launch_cbatch_prf(const CbPrfArgs<NL> &, int, in
 // hb_kern_cpv.hip / hb_kern_cpv64.hip
 template <int NL> hipError_t hb_launch_cpv_prf(const CpvPrfArgs<NL> &, int, int, hipStream_t);
 template <int NL> hipError_t hb_launch_cpv_sum(const CpvSumArgs<NL> &, u32, hipStream_t);
+// hb_kern_mixed.hip / hb_kern_mixed64.hip
+template <int NL> hipError_t hb_launch_mixed_mont(const MxMontArgs<NL> &, u32, hipStream_t);
+template <int NL> hipError_t hb_launch_mixed_sum(const MxSumArgs<NL> &, u32, hipStream_t);
+template <int NL> hipError_t hb_launch_vmixed_prf(const VmPrfArgs<NL> &, int, int, hipStream_t);
+template <int NL> hipError_t hb_launch_vmixed_sum(const VmSumArgs<NL> &, u32, hipStream_t);
 
 namespace {
 
@@ -3349,6 +3356,337 @@ int cxx_prove_many_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const Prim
     });
 }
 
+// ------------------------------------------------------------------ prove and verify, many owners
+// hb_prove_mixed and hb_verify_rhs_mixed: hb_prove_many and hb_verify_rhs_many
+// for proofs that each name their own prime, sector count and key length.
+// The entry points check every descriptor, look every prime up in the call's
+// cache of Montgomery constants (HbPrimeCache: once per distinct prime) and
+// split the proofs into classes of one limb count and one AES round count
+// (hb_mixed_partition); a class is planned and run here exactly as the
+// one-prime call plans and runs its proofs -- same caps, same fall-through
+// rules, same queue order -- with what that call keeps in the kernel arguments
+// (ModP, R^2, C, ss, S, tw) in one more uploaded section of per-proof records
+// (MxRec), the ragged result columns / alpha slots as prefix sums, and a
+// workgroup table each for the sum launch and the conversion pass
+// (hb_mixed_host.hpp).  Launches per group: 3 (prove), 2 (verify).
+// last_launches accumulates over the groups of every class and the single
+// calls of the proofs that fall through.
+struct MixedCall {
+    HbPrimeCache primes;
+    std::vector<size_t> prime_of;   // per proof: its entry in `primes`
+    std::vector<PrimeInfo> pi;      // per proof
+};
+
+template <int NL>
+void fill_rec(const HbMxPrime &P, const PrimeInfo &pi, u32 S, u64 col0, u64 slot0, MxRec<NL> &R) {
+    memset(&R, 0, sizeof R);
+    for (int t = 0; t < NL; ++t) {
+        R.mod.p[t] = P.p[t];
+        R.r2[t] = P.r2[t];
+    }
+    R.mod.pinv = P.pinv;
+    R.mod.inv_scaled = P.inv_scaled;
+    R.C = (u64)pi.ss * S;
+    R.ss = pi.ss;
+    R.S = S;
+    R.tw = pi.tw;
+    R.col0 = (u32)col0;
+    R.slot0 = (u32)slot0;
+}
+static_assert(sizeof(MxWg) == sizeof(HbMxWg) && sizeof(MxWg) == HB_MXWG_BYTES && HB_MX_MONT_WG == HB_MX_MONT_TERMS,
+              "the workgroup tables are the host header's");
+// proofs x columns and alpha slots fit the records' 32-bit col0 / slot0 and
+// the sum launches' grid: each column or slot costs NL 4 >= 32 bytes of a
+// group's HB_BATCH_BYTES
+static_assert(HB_BATCH_BYTES / (8 * 4) <= 0x7fffffffull, "the byte cap bounds col0, slot0 and the grids");
+
+template <int NL>
+int prove_mixed_impl(hb_ctx *c, const hb_prove_mixed_desc *descs, const std::vector<u64> &cls, int nr, u32 flags,
+                     const MixedCall &MC) {
+    const HbBatchSizes z = batch_sizes<NL>();
+    const u64 rec = sizeof(MxRec<NL>);
+    const bool data_dev = (flags & HB_DATA_ON_DEVICE) != 0, tags_dev = (flags & HB_TAGS_ON_DEVICE) != 0;
+    const u64 cap_chunks = hb_test_cap(sw_env(c, "HB_TEST_BATCH_CHUNKS"));
+    const bool no_upload = sw_env(c, "HB_NO_PROVE_UPLOAD") || sw_env(c, "HB_TEST_PROVE_BATCH");
+    auto jobs_of = [](u64 n) { return 2 * ((n + 15) / 16); };
+    auto shape_of = [&](u64 i) {
+        const PrimeInfo &pi = MC.pi[(size_t)i];
+        const u32 S = (u32)descs[i].sectors;
+        return ProveShape{(u64)pi.ss * S, S, pi.tw, data_dev, tags_dev};
+    };
+    // which proofs batch, of the proofs with a challenge (the others: zero
+    // sums, no GPU work, as prove_impl)
+    std::vector<u64> cand;
+    std::vector<HbCbItemReq> req;
+    for (u64 i : cls) {
+        const hb_prove_desc &D = descs[i].d;
+        const ProveShape E = shape_of(i);
+        const u64 n = D.chunks;
+        if (n == 0) {
+            memset(D.mu_out, 0, (size_t)E.S * E.tw);
+            memset(D.sigma_out, 0, E.tw);
+            continue;
+        }
+        cand.push_back(i);
+        HbCbItemReq R = {};
+        R.bytes = hb_mprove_cost(z, rec, jobs_of(n), n, E.S, E.up_files(D));
+        const bool batched = n <= cap_chunks && n < (1ull << 31) && use_quad(c, 2 * n) && !(no_upload && !data_dev) &&
+                             E.uploadable(D, n) && R.bytes <= HB_BATCH_BYTES;
+        R.units = batched ? n : ~0ull;   // over any bound: the single call
+        req.push_back(R);
+    }
+    const u64 bound = cap_chunks < (1ull << 31) ? cap_chunks : (1ull << 31);
+    const HbCbPlan plan = hb_batch_groups(req.data(), req.size(), bound, cap_chunks, HB_BATCH_BYTES);
+    const size_t key_len = nr == 10 ? 16 : nr == 12 ? 24 : 32;
+
+    auto run_group = [&](const HbCbGroup &G) -> int {
+        const u64 np = G.nitems, terms = G.units;
+        const u64 *g = plan.order.data() + G.item0;   // positions in cand
+        u64 nj = 0, up_files = 0;
+        std::vector<u32> Sv((size_t)np), nv((size_t)np);
+        for (u64 f = 0; f < np; ++f) {
+            const u64 i = cand[g[f]];
+            nj += jobs_of(descs[i].d.chunks);
+            up_files += shape_of(i).up_files(descs[i].d);
+            Sv[(size_t)f] = (u32)descs[i].sectors;
+            nv[(size_t)f] = (u32)descs[i].d.chunks;
+        }
+        std::vector<u64> col0;
+        const u64 cols = hb_mixed_prefix(Sv.data(), np, 1, col0);
+        const u64 nmwg = hb_mixed_mont_wgs(nv.data(), np, nullptr);
+        const HbArena L = hb_mprove_arena(z, rec, np, nj, cols, nmwg, up_files, terms);
+        if (int rc = group_arenas(c, L, HB_MXP_RES)) return rc;
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        PrfParams<2> *hpidx = L.at<PrfParams<2>>(host, HB_MXP_PIDX);
+        PrfParams<NL> *hpv = L.at<PrfParams<NL>>(host, HB_MXP_PV);
+        PbProof *hproofs = L.at<PbProof>(host, HB_MXP_PROOFS);
+        MxRec<NL> *hrecs = L.at<MxRec<NL>>(host, HB_MXP_RECS);
+        PbWaveJob *hjobs = L.at<PbWaveJob>(host, HB_MXP_JOBS);
+        if (hb_mixed_sum_wgs(Sv.data(), np, L.at<HbMxWg>(host, HB_MXP_SUMWG)) != cols ||
+            hb_mixed_mont_wgs(nv.data(), np, L.at<HbMxWg>(host, HB_MXP_MONTWG)) != nmwg)
+            return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        u64 o_next = L.off[HB_MXP_DATA];
+        u32 nb_idx = 0, nb_v = 0;
+        RangeCache<2> PI0;
+        RangeCache<NL> PV0;
+        for (u64 f = 0; f < np; ++f) {
+            const u64 i = cand[g[f]];
+            const hb_prove_desc &D = descs[i].d;
+            const PrimeInfo &pi = MC.pi[(size_t)i];
+            const ProveShape E = shape_of(i);
+            if (!PI0.get(D.chal_key, key_len, D.ntags) || !PV0.get(D.chal_key, key_len, D.vmax_be, (size_t)D.vmax_len))
+                return fail(c, HB_EINVAL, "invalid challenge key");
+            AesKey kc;
+            if (!aes_expand(D.chal_key, key_len, kc)) return fail(c, HB_EINVAL, "invalid challenge key");
+            if (kc.nr != nr) return fail(c, HB_EHIP, "internal: AES round counts differ");
+            schedule<2>(PI0.tmpl, kc, hpidx[f]);
+            schedule<NL>(PV0.tmpl, kc, hpv[f]);
+            if (PI0.tmpl.nb > nb_idx) nb_idx = PI0.tmpl.nb;
+            if (PV0.tmpl.nb > nb_v) nb_v = PV0.tmpl.nb;
+            const unsigned char *ddata = stage_in(data_dev, D.data, D.len, host, dev, o_next);
+            const unsigned char *dtags = stage_in(tags_dev, D.tags, D.ntags * pi.tw, host, dev, o_next);
+            // per proof, with THIS proof's ss, tw and C
+            const bool load16 = pi.ss == 4u * NL && pi.tw == 4u * NL && E.C % 16 == 0 && (uintptr_t)ddata % 16 == 0 &&
+                                (uintptr_t)dtags % 16 == 0;
+            hproofs[f] = PbProof{plan.ubase[(size_t)(G.item0 + f)], ddata, D.len, dtags, D.ntags, (u32)D.chunks,
+                                 load16 ? HB_PB_LOAD16 : 0u};
+            fill_rec<NL>(MC.primes.primes[MC.prime_of[(size_t)i]], pi, E.S, col0[(size_t)f], 0, hrecs[f]);
+        }
+        // queue order, longest wave-job first, as in prove_many_impl
+        const u32 kind0 = nb_v >= nb_idx ? HB_PB_V : HB_PB_IDX;
+        u64 j = 0;
+        for (u32 k = 0; k < 2; ++k)
+            for (u64 f = 0; f < np; ++f) push_jobs16(hjobs, j, f, k == 0 ? kind0 : 1u - kind0, hproofs[f].chunks);
+        if (j != nj || o_next != L.up_bytes) return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        unsigned long long qs[2 * HB_QSLOT];
+        auto launch = [&]() -> int {
+            PbPrfArgs<NL> A;
+            memset(&A, 0, sizeof A);
+            A.pidx = L.at<const PrfParams<2>>(dev, HB_MXP_PIDX);
+            A.pv = L.at<const PrfParams<NL>>(dev, HB_MXP_PV);
+            A.proofs = L.at<const PbProof>(dev, HB_MXP_PROOFS);
+            A.jobs = L.at<const PbWaveJob>(dev, HB_MXP_JOBS);
+            A.njobs = nj;
+            A.idx = L.at<u64>(dev, HB_MXP_IDX);
+            A.vv = L.at<u32>(dev, HB_MXP_VV);
+            A.t0 = c->t0;
+            A.queue = c->queue;
+            HB_CHECK(hb_launch_pbatch_prf<NL>(A, nr, batch_grid(c, (nj + 15) / 16), c->stream), "hb_pbatch_prf_kernel launch");
+            MxMontArgs<NL> T;
+            memset(&T, 0, sizeof T);
+            T.recs = L.at<const MxRec<NL>>(dev, HB_MXP_RECS);
+            T.proofs = A.proofs;
+            T.wgs = L.at<const MxWg>(dev, HB_MXP_MONTWG);
+            T.vv = A.vv;
+            HB_CHECK(hb_launch_mixed_mont<NL>(T, (u32)nmwg, c->stream), "hb_mixed_mont_kernel launch");
+            MxSumArgs<NL> M;
+            memset(&M, 0, sizeof M);
+            M.recs = T.recs;
+            M.proofs = A.proofs;
+            M.wgs = L.at<const MxWg>(dev, HB_MXP_SUMWG);
+            M.idx = A.idx;
+            M.vm = A.vv;
+            M.res = L.at<u32>(dev, HB_MXP_RES);
+            HB_CHECK(hb_launch_mixed_sum<NL>(M, (u32)cols, c->stream), "hb_mixed_sum_kernel launch");
+            c->last_launches += 3;
+            return 0;
+        };
+        // slots 0 (wave-job counter, index) and 1 (v)
+        if (int rc = group_transport(c, L, 2, launch, HB_MXP_RES, "hipMemcpyAsync(D2H results)", qs, "mixed batched prove"))
+            return rc;
+        if (qs[2] || qs[HB_QSLOT + 2]) return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate");
+        for (u64 f = 0; f < np; ++f) {
+            const u64 i = cand[g[f]];
+            prove_results<NL>(shape_of(i), (const u32 *)host + col0[(size_t)f] * NL, descs[i].d);
+        }
+        return 0;
+    };
+
+    int rc = 0;
+    for (size_t k = 0; k < plan.groups.size() && !rc; ++k) rc = run_group(plan.groups[k]);
+    return batch_finish(c, rc, !plan.groups.empty(), 2, plan.through, true, [&](u64 k) -> int {
+        const u64 i = cand[k];
+        const hb_prove_desc &D = descs[i].d;
+        return prove_impl<NL>(c, descs[i].p_be, (size_t)descs[i].p_len, MC.pi[(size_t)i], (u32)descs[i].sectors, D.chal_key,
+                              key_len, 0, UINT64_MAX, D.chunks, D.vmax_be, (size_t)D.vmax_len, D.tags, D.ntags, D.data, D.len,
+                              flags, D.mu_out, D.sigma_out);
+    });
+}
+
+template <int NL>
+int verify_mixed_impl(hb_ctx *c, const hb_verify_mixed_desc *descs, const std::vector<u64> &cls, int nr, const MixedCall &MC) {
+    const HbBatchSizes z = batch_sizes<NL>();
+    const u64 rec = sizeof(MxRec<NL>);
+    const u64 cap_chunks = hb_test_cap(sw_env(c, "HB_TEST_BATCH_CHUNKS"));
+    const size_t key_len = nr == 10 ? 16 : nr == 12 ? 24 : 32;   // the class's: state keys and, of a batched proof, the challenge key
+    auto jobs_of = [](u64 n, u64 S) { return (S + 15) / 16 + 2 * ((n + 15) / 16); };
+    // which proofs batch
+    const u64 ncls = cls.size();
+    std::vector<HbCbItemReq> req((size_t)ncls);
+    for (u64 k = 0; k < ncls; ++k) {
+        const hb_verify_mixed_desc &X = descs[cls[k]];
+        const u64 n = X.d.chunks;
+        const bool same_nr = hb_mx_rounds(X.key_len) == hb_mx_rounds(X.chal_key_len);
+        req[(size_t)k].bytes = hb_mverify_cost(z, rec, jobs_of(n, X.sectors), n, X.sectors);
+        const bool batched = same_nr && n <= cap_chunks && n < (1ull << 31) && (n == 0 || use_quad(c, 2 * n)) &&
+                             req[(size_t)k].bytes <= HB_BATCH_BYTES;
+        req[(size_t)k].units = batched ? n : ~0ull;   // over any bound: the single call
+    }
+    const u64 bound = cap_chunks < (1ull << 31) ? cap_chunks : (1ull << 31);
+    const HbCbPlan plan = hb_batch_groups(req.data(), ncls, bound, cap_chunks, HB_BATCH_BYTES);
+
+    auto run_group = [&](const HbCbGroup &G) -> int {
+        const u64 np = G.nitems, terms = G.units;
+        const u64 *g = plan.order.data() + G.item0;   // positions in cls
+        u64 nj = 0;
+        std::vector<u32> Sv((size_t)np);
+        for (u64 f = 0; f < np; ++f) {
+            const hb_verify_mixed_desc &X = descs[cls[g[f]]];
+            nj += jobs_of(X.d.chunks, X.sectors);
+            Sv[(size_t)f] = (u32)X.sectors;
+        }
+        std::vector<u64> slot0;
+        const u64 slots = hb_mixed_prefix(Sv.data(), np, 0, slot0);
+        const HbArena L = hb_mverify_arena(z, rec, np, nj, terms, slots);
+        if (int rc = group_arenas(c, L, HB_MXV_RES)) return rc;
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        PrfParams<2> *hpidx = L.at<PrfParams<2>>(host, HB_MXV_PIDX);
+        PrfParams<NL> *hprf = L.at<PrfParams<NL>>(host, HB_MXV_PRF);
+        VbProof *hproofs = L.at<VbProof>(host, HB_MXV_PROOFS);
+        MxRec<NL> *hrecs = L.at<MxRec<NL>>(host, HB_MXV_RECS);
+        VbWaveJob *hjobs = L.at<VbWaveJob>(host, HB_MXV_JOBS);
+        u32 *hmu = L.at<u32>(host, HB_MXV_MU);
+        // range templates, rebuilt only when the range differs from the last
+        // proof's: here the prime's as well
+        const uint8_t one = 1;
+        RangeCache<2> PI0;
+        RangeCache<NL> PV0, PP0;
+        for (u64 f = 0; f < np; ++f) {
+            const u64 i = cls[g[f]];
+            const hb_verify_mixed_desc &X = descs[i];
+            const hb_verify_desc &D = X.d;
+            const PrimeInfo &pi = MC.pi[(size_t)i];
+            const u32 S = (u32)X.sectors;
+            const u64 nstate = D.state_chunks ? D.state_chunks : 1;   // (no index is drawn when chunks == 0)
+            const uint8_t *vm = D.chunks ? D.vmax_be : &one;
+            const size_t vl = D.chunks ? (size_t)D.vmax_len : 1;
+            if (!PI0.get(D.chal_key, key_len, nstate) || !PV0.get(D.chal_key, key_len, vm, vl) ||
+                !PP0.get(D.f_key, key_len, X.p_be, (size_t)X.p_len))
+                return fail(c, HB_EINVAL, "invalid key");
+            AesKey kf, ka, kc;
+            if (!aes_expand(D.f_key, key_len, kf) || !aes_expand(D.alpha_key, key_len, ka) ||
+                !aes_expand(D.chal_key, (size_t)X.chal_key_len, kc))
+                return fail(c, HB_EINVAL, "invalid key");
+            if (kf.nr != nr || ka.nr != nr || kc.nr != nr) return fail(c, HB_EHIP, "internal: AES round counts differ");
+            schedule<2>(PI0.tmpl, kc, hpidx[f]);
+            schedule<NL>(PP0.tmpl, kf, hprf[3 * f + HB_VB_IDXF]);
+            schedule<NL>(PV0.tmpl, kc, hprf[3 * f + HB_VB_V]);
+            schedule<NL>(PP0.tmpl, ka, hprf[3 * f + HB_VB_ALPHA]);
+            hproofs[f] = VbProof{plan.ubase[(size_t)(G.item0 + f)], (u32)D.chunks, 0u};
+            fill_rec<NL>(MC.primes.primes[MC.prime_of[(size_t)i]], pi, S, 0, slot0[(size_t)f], hrecs[f]);
+            // mu_j: tw big-endian bytes -> NL little-endian limbs
+            for (u32 j = 0; j < S; ++j)
+                be_to_limbs(D.mu + (size_t)j * pi.tw, pi.tw, hmu + ((size_t)slot0[(size_t)f] + j) * NL, NL);
+        }
+        // queue order, longest wave-job first, as in verify_many_impl
+        u64 j = 0;
+        for (u64 f = 0; f < np; ++f) push_jobs16(hjobs, j, f, HB_VB_IDXF, hproofs[f].chunks);
+        for (u64 f = 0; f < np; ++f) push_jobs16(hjobs, j, f, HB_VB_ALPHA, Sv[(size_t)f]);
+        for (u64 f = 0; f < np; ++f) push_jobs16(hjobs, j, f, HB_VB_V, hproofs[f].chunks);
+        if (j != nj) return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        unsigned long long qs[3 * HB_QSLOT];
+        auto launch = [&]() -> int {
+            VmPrfArgs<NL> A;
+            memset(&A, 0, sizeof A);
+            A.b.pidx = L.at<const PrfParams<2>>(dev, HB_MXV_PIDX);
+            A.b.prf = L.at<const PrfParams<NL>>(dev, HB_MXV_PRF);
+            A.b.proofs = L.at<const VbProof>(dev, HB_MXV_PROOFS);
+            A.b.jobs = L.at<const VbWaveJob>(dev, HB_MXV_JOBS);
+            A.b.njobs = nj;
+            A.b.fv = L.at<u32>(dev, HB_MXV_FV);
+            A.b.vv = L.at<u32>(dev, HB_MXV_VV);
+            A.b.av = L.at<u32>(dev, HB_MXV_AV);
+            A.b.t0 = c->t0;
+            A.b.queue = c->queue;
+            A.recs = L.at<const MxRec<NL>>(dev, HB_MXV_RECS);
+            HB_CHECK(hb_launch_vmixed_prf<NL>(A, nr, batch_grid(c, (nj + 15) / 16), c->stream), "hb_vmixed_prf_kernel launch");
+            VmSumArgs<NL> M;
+            memset(&M, 0, sizeof M);
+            M.recs = A.recs;
+            M.proofs = A.b.proofs;
+            M.fv = A.b.fv;
+            M.vv = A.b.vv;
+            M.av = A.b.av;
+            M.mu = L.at<const u32>(dev, HB_MXV_MU);
+            M.res = L.at<u32>(dev, HB_MXV_RES);
+            HB_CHECK(hb_launch_vmixed_sum<NL>(M, (u32)np, c->stream), "hb_vmixed_sum_kernel launch");
+            c->last_launches += 2;
+            return 0;
+        };
+        // slots 0 (wave-job counter, index + F), 1 (v) and 2 (alpha)
+        if (int rc = group_transport(c, L, 3, launch, HB_MXV_RES, "hipMemcpyAsync(D2H results)", qs, "mixed batched verify"))
+            return rc;
+        if (qs[2] || qs[HB_QSLOT + 2] || qs[2 * HB_QSLOT + 2])
+            return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate");
+        for (u64 f = 0; f < np; ++f) {
+            const u64 i = cls[g[f]];
+            to_be((const u32 *)host + f * NL, NL, descs[i].d.rhs_out, MC.pi[(size_t)i].tw);
+        }
+        return 0;
+    };
+
+    int rc = 0;
+    for (size_t k = 0; k < plan.groups.size() && !rc; ++k) rc = run_group(plan.groups[k]);
+    return batch_finish(c, rc, !plan.groups.empty(), 3, plan.through, true, [&](u64 k) -> int {
+        const u64 i = cls[k];
+        const hb_verify_mixed_desc &X = descs[i];
+        const hb_verify_desc &D = X.d;
+        return verify_impl<NL>(c, X.p_be, (size_t)X.p_len, MC.pi[(size_t)i], (u32)X.sectors, D.f_key, D.alpha_key,
+                               (size_t)X.key_len, D.state_chunks, D.chal_key, (size_t)X.chal_key_len, D.chunks, D.vmax_be,
+                               (size_t)D.vmax_len, D.mu, D.rhs_out);
+    });
+}
+
 }  // namespace
 
 // ================================================================== C ABI
@@ -3731,41 +4069,67 @@ int entry_begin(hb_ctx *c, const uint8_t *p_be, size_t p_len, PrimeInfo &pi, siz
     return 0;
 }
 
-// What hb_prove (cxx: hb_prove(HB_PRF_CXX)) checks per call, for every proof
-// before any GPU work
+// What hb_prove (cxx: hb_prove(HB_PRF_CXX)) checks per call, for one proof
+// (who: "proof i: ") and for every proof before any GPU work
+int check_prove_desc(hb_ctx *c, const PrimeInfo &pi, const hb_prove_desc &D, const std::string &who, bool cxx) {
+    if (!D.chal_key) return fail(c, HB_EINVAL, who + "the challenge key is NULL");
+    if (!D.mu_out || !D.sigma_out) return fail(c, HB_EINVAL, who + "mu_out or sigma_out is NULL");
+    if (!D.vmax_be && D.vmax_len) return fail(c, HB_EINVAL, who + "v_max is NULL");
+    if (D.ntags == 0) return fail(c, HB_EINVAL, who + "tag is empty");
+    if (!D.tags) return fail(c, HB_EINVAL, who + "tags buffer is NULL");
+    if (!D.data && D.len) return fail(c, HB_EINVAL, who + "data buffer is NULL");
+    const int vbits = bitlen_be(D.vmax_be, (size_t)D.vmax_len);
+    if (vbits == 0) return fail(c, HB_EINVAL, who + "v_max must be positive");
+    if (vbits > 32 * pi.nl) return fail(c, HB_EUNSUPPORTED, who + "v_max wider than the prime's limb count");
+    if (cxx && (D.ntags >> 32)) return fail(c, HB_EUNSUPPORTED, who + "cxx prove: more than 2^32 - 1 tags");
+    return 0;
+}
 int check_prove_descs(hb_ctx *c, const PrimeInfo &pi, const hb_prove_desc *proofs, u64 n, bool cxx) {
-    for (u64 i = 0; i < n; ++i) {
-        const hb_prove_desc &D = proofs[i];
-        const std::string who = "proof " + std::to_string(i) + ": ";
-        if (!D.chal_key) return fail(c, HB_EINVAL, who + "the challenge key is NULL");
-        if (!D.mu_out || !D.sigma_out) return fail(c, HB_EINVAL, who + "mu_out or sigma_out is NULL");
-        if (!D.vmax_be && D.vmax_len) return fail(c, HB_EINVAL, who + "v_max is NULL");
-        if (D.ntags == 0) return fail(c, HB_EINVAL, who + "tag is empty");
-        if (!D.tags) return fail(c, HB_EINVAL, who + "tags buffer is NULL");
-        if (!D.data && D.len) return fail(c, HB_EINVAL, who + "data buffer is NULL");
-        const int vbits = bitlen_be(D.vmax_be, (size_t)D.vmax_len);
-        if (vbits == 0) return fail(c, HB_EINVAL, who + "v_max must be positive");
-        if (vbits > 32 * pi.nl) return fail(c, HB_EUNSUPPORTED, who + "v_max wider than the prime's limb count");
-        if (cxx && (D.ntags >> 32)) return fail(c, HB_EUNSUPPORTED, who + "cxx prove: more than 2^32 - 1 tags");
-    }
+    for (u64 i = 0; i < n; ++i)
+        if (int rc = check_prove_desc(c, pi, proofs[i], "proof " + std::to_string(i) + ": ", cxx)) return rc;
     return 0;
 }
 
-// What hb_verify_rhs (cxx: hb_cxx_verify_rhs) checks per call, for every proof
-// before any GPU work
+// What hb_verify_rhs (cxx: hb_cxx_verify_rhs) checks per call, for one proof
+// and for every proof before any GPU work
+int check_verify_desc(hb_ctx *c, const PrimeInfo &pi, const hb_verify_desc &D, const std::string &who, bool cxx) {
+    if (!D.f_key || !D.alpha_key || !D.chal_key) return fail(c, HB_EINVAL, who + "a key is NULL");
+    if (!D.mu || !D.rhs_out) return fail(c, HB_EINVAL, who + "mu or rhs_out is NULL");
+    if (!D.vmax_be && D.vmax_len) return fail(c, HB_EINVAL, who + "v_max is NULL");
+    if (cxx && (D.state_chunks >> 32)) return fail(c, HB_EUNSUPPORTED, who + "cxx verify: more than 2^32 - 1 blocks");
+    if (D.chunks && D.state_chunks == 0) return fail(c, HB_EINVAL, who + "state has no chunks");
+    const int vbits = bitlen_be(D.vmax_be, (size_t)D.vmax_len);
+    if (D.chunks && vbits == 0) return fail(c, HB_EINVAL, who + "v_max must be positive");
+    if (vbits > 32 * pi.nl) return fail(c, HB_EUNSUPPORTED, who + "v_max wider than the prime's limb count");
+    return 0;
+}
 int check_verify_descs(hb_ctx *c, const PrimeInfo &pi, const hb_verify_desc *proofs, u64 n, bool cxx) {
-    for (u64 i = 0; i < n; ++i) {
-        const hb_verify_desc &D = proofs[i];
-        const std::string who = "proof " + std::to_string(i) + ": ";
-        if (!D.f_key || !D.alpha_key || !D.chal_key) return fail(c, HB_EINVAL, who + "a key is NULL");
-        if (!D.mu || !D.rhs_out) return fail(c, HB_EINVAL, who + "mu or rhs_out is NULL");
-        if (!D.vmax_be && D.vmax_len) return fail(c, HB_EINVAL, who + "v_max is NULL");
-        if (cxx && (D.state_chunks >> 32)) return fail(c, HB_EUNSUPPORTED, who + "cxx verify: more than 2^32 - 1 blocks");
-        if (D.chunks && D.state_chunks == 0) return fail(c, HB_EINVAL, who + "state has no chunks");
-        const int vbits = bitlen_be(D.vmax_be, (size_t)D.vmax_len);
-        if (D.chunks && vbits == 0) return fail(c, HB_EINVAL, who + "v_max must be positive");
-        if (vbits > 32 * pi.nl) return fail(c, HB_EUNSUPPORTED, who + "v_max wider than the prime's limb count");
-    }
+    for (u64 i = 0; i < n; ++i)
+        if (int rc = check_verify_desc(c, pi, proofs[i], "proof " + std::to_string(i) + ": ", cxx)) return rc;
+    return 0;
+}
+
+// What the mixed calls check of a proof's own prime, key lengths and sectors:
+// entry_begin's checks in entry_begin's order, hb_last_error naming the proof
+int check_mixed_head(hb_ctx *c, const std::string &who, const uint8_t *p_be, u64 p_len, u64 key_len, u64 chal_key_len,
+                     u64 sectors, PrimeInfo &pi) {
+    int rc = parse_prime(c, p_be, (size_t)p_len, pi);
+    if (!rc) rc = check_key(c, (size_t)key_len);
+    if (!rc) rc = check_key(c, (size_t)chal_key_len);
+    if (!rc && sectors == 0) rc = fail(c, HB_EINVAL, "sectors must be positive");
+    if (!rc && (sectors >> 32)) rc = fail(c, HB_EINVAL, "sectors must be below 2^32");
+    if (rc) c->err = who + c->err;
+    return rc;
+}
+
+// The classes of a mixed call, one after the other (run: class -> status).
+template <class Run>
+int mixed_classes(hb_ctx *c, const std::vector<uint32_t> &nl, const std::vector<uint32_t> &nr, Run &&run) {
+    c->last_launches = 0;
+    c->last_ms = 0.0;
+    c->ph_valid = false;
+    for (const HbMxClass &K : hb_mixed_partition(nl.data(), nr.data(), nl.size()))
+        if (int rc = run(K)) return rc;
     return 0;
 }
 
@@ -3923,6 +4287,64 @@ int hb_verify_rhs_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t se
     HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
     return by_nl(c, pi.nl, [&](auto NL) {
         return verify_many_impl<HB_NL(NL)>(c, p_be, p_len, pi, sectors, key_len, chal_key_len, proofs, nproofs);
+    });
+}
+
+int hb_prove_mixed(hb_ctx *c, const hb_prove_mixed_desc *proofs, uint64_t nproofs, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (flags & ~(uint32_t)(HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE))
+        return fail(c, HB_EUNSUPPORTED, "hb_prove_mixed takes only HB_DATA_ON_DEVICE and HB_TAGS_ON_DEVICE");
+    if (nproofs == 0) return 0;
+    if (!proofs) return fail(c, HB_EINVAL, "proofs is NULL");
+    MixedCall MC;
+    MC.pi.resize((size_t)nproofs);
+    MC.prime_of.resize((size_t)nproofs);
+    std::vector<uint32_t> nl((size_t)nproofs), nr((size_t)nproofs);
+    for (u64 i = 0; i < nproofs; ++i) {
+        const hb_prove_mixed_desc &X = proofs[i];
+        const std::string who = "proof " + std::to_string(i) + ": ";
+        if (int rc = check_mixed_head(c, who, X.p_be, X.p_len, X.key_len, X.key_len, X.sectors, MC.pi[(size_t)i])) return rc;
+        if (int rc = check_prove_desc(c, MC.pi[(size_t)i], X.d, who, false)) return rc;
+        nl[(size_t)i] = (uint32_t)MC.pi[(size_t)i].nl;
+        nr[(size_t)i] = hb_mx_rounds(X.key_len);
+    }
+    for (u64 i = 0; i < nproofs; ++i)
+        MC.prime_of[(size_t)i] = MC.primes.get(proofs[i].p_be, (size_t)proofs[i].p_len, nl[(size_t)i]);
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    return mixed_classes(c, nl, nr, [&](const HbMxClass &K) {
+        return by_nl(c, (int)K.nl, [&](auto NL) {
+            return prove_mixed_impl<HB_NL(NL)>(c, proofs, K.items, (int)K.nr, flags, MC);
+        });
+    });
+}
+
+int hb_verify_rhs_mixed(hb_ctx *c, const hb_verify_mixed_desc *proofs, uint64_t nproofs, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (flags) return fail(c, HB_EUNSUPPORTED, "hb_verify_rhs_mixed takes no flags");
+    if (nproofs == 0) return 0;
+    if (!proofs) return fail(c, HB_EINVAL, "proofs is NULL");
+    MixedCall MC;
+    MC.pi.resize((size_t)nproofs);
+    MC.prime_of.resize((size_t)nproofs);
+    std::vector<uint32_t> nl((size_t)nproofs), nr((size_t)nproofs);
+    for (u64 i = 0; i < nproofs; ++i) {
+        const hb_verify_mixed_desc &X = proofs[i];
+        const std::string who = "proof " + std::to_string(i) + ": ";
+        if (int rc = check_mixed_head(c, who, X.p_be, X.p_len, X.key_len, X.chal_key_len, X.sectors, MC.pi[(size_t)i]))
+            return rc;
+        if (int rc = check_verify_desc(c, MC.pi[(size_t)i], X.d, who, false)) return rc;
+        nl[(size_t)i] = (uint32_t)MC.pi[(size_t)i].nl;
+        nr[(size_t)i] = hb_mx_rounds(X.key_len);
+    }
+    for (u64 i = 0; i < nproofs; ++i)
+        MC.prime_of[(size_t)i] = MC.primes.get(proofs[i].p_be, (size_t)proofs[i].p_len, nl[(size_t)i]);
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    return mixed_classes(c, nl, nr, [&](const HbMxClass &K) {
+        return by_nl(c, (int)K.nl, [&](auto NL) {
+            return verify_mixed_impl<HB_NL(NL)>(c, proofs, K.items, (int)K.nr, MC);
+        });
     });
 }
 

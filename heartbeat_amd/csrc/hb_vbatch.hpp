@@ -55,8 +55,18 @@ struct VbHandler {
     __device__ __forceinline__ void accept(u64 job, const u32 v[NL]) const { hb_store_limbs<NL>(out + job * NL, v); }
 };
 
-template <int NL, int NR>
-__global__ __launch_bounds__(HB_ENGINE_WG) void hb_vbatch_prf_kernel(VbPrfArgs<NL> A) {
+// Where a proof's alpha values land in A.av, in slots of NL limbs: with one S
+// for the batch, proof * S.  (hb_mixed.hpp has the other one: each proof's
+// own first slot, from its record.)
+struct VbAlphaShared {
+    u32 S;
+    __device__ __forceinline__ u64 operator()(u32 proof) const { return (u64)proof * S; }
+};
+
+// The PRF launch's body, shared by hb_vbatch_prf_kernel and the mixed-owner
+// batch's hb_vmixed_prf_kernel: they differ in AlphaBase alone.
+template <int NL, int NR, class AlphaBase>
+__device__ __forceinline__ void hb_vbatch_prf_body(const VbPrfArgs<NL> &A, const AlphaBase &alpha_base) {
     __shared__ __attribute__((aligned(16))) u32 lds[HB_LDS_WORDS];
     __shared__ u64 xidx[HB_ENGINE_WG / 64][16];
     hb_fill_lds(lds, A.t0);
@@ -105,10 +115,15 @@ __global__ __launch_bounds__(HB_ENGINE_WG) void hb_vbatch_prf_kernel(VbPrfArgs<N
         }
         PrfParams<NL> P;
         hb_load_uniform(A.prf, 3u * proof + kind, P);
-        u32 *out = kind == HB_VB_ALPHA ? A.av + (u64)proof * A.S * NL : (idxf ? A.fv : A.vv) + V.obase * NL;
+        u32 *out = kind == HB_VB_ALPHA ? A.av + alpha_base(proof) * NL : (idxf ? A.fv : A.vv) + V.obase * NL;
         VbHandler<NL> h{slot, first, out, idxf};
         hb_engine_quad<NL, NR, VbHandler<NL>>(h, L, P, stop, q, 16, first);
     }
+}
+
+template <int NL, int NR>
+__global__ __launch_bounds__(HB_ENGINE_WG) void hb_vbatch_prf_kernel(VbPrfArgs<NL> A) {
+    hb_vbatch_prf_body<NL, NR>(A, VbAlphaShared{A.S});
 }
 
 // rhs of one proof per workgroup: sum_i v_i F_i + sum_j alpha_j mu_j mod p

@@ -449,6 +449,67 @@ int hb_verify_rhs_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t 
                        size_t key_len, size_t chal_key_len,
                        const hb_verify_desc *proofs, uint64_t nproofs, uint32_t flags);
 
+/* hb_prove_many for the proofs of many owners: every proof names its own
+ * prime, `sectors` and challenge key length.  A PySwizzle instance draws its
+ * own prime (PySwizzle.py:250-251) and hands it to the storage node with the
+ * public beat (:277), so a node that answers an audit period's challenges for
+ * several owners has one prime per owner, not one per batch.  Replaces that
+ * node's loop of hb_prove (PySwizzle.py:333-370 per proof): proof i's mu_out
+ * (its own sectors * hb_width(its own p) bytes) and sigma_out receive exactly
+ * the bytes hb_prove writes for the same arguments, PySwizzle's KeyedPRF.
+ * The proofs are split into classes by the prime's limb count (256 / 512 /
+ * 1024 / 2048 bits) and the key's AES round count; a class is grouped and run
+ * as hb_prove_many runs a batch -- per group one H2D copy, one PRF launch,
+ * one conversion pass, one sum launch, one D2H copy -- with each proof's
+ * modulus, geometry and result columns in a per-proof device record.  The
+ * Montgomery constants are computed once per distinct prime of the call.
+ * Proofs the batch path does not take (as in hb_prove_many: more challenge
+ * indices than the quad engine places, a host file above max(2 chunks C,
+ * 8 MiB), host data with device tags) go through the single prove under their
+ * own prime and `sectors` inside the same call.
+ * flags applies to the whole call: HB_DATA_ON_DEVICE and/or
+ * HB_TAGS_ON_DEVICE; anything else returns HB_EUNSUPPORTED.  nproofs == 0
+ * returns HB_OK; chunks == 0 gives zero mu and sigma.  Every descriptor is
+ * checked before any GPU work: what hb_prove rejects for that proof's own
+ * arguments (a prime above 2048 bits or below 2^7, an even prime, sectors ==
+ * 0, a key length other than 16 / 24 / 32, ntags == 0, v_max == 0, a v_max
+ * wider than THAT proof's limb count, a NULL buffer) fails the whole call
+ * with hb_prove's code, hb_last_error names the proof ("proof 3: ..."), and
+ * no result buffer is written. */
+typedef struct hb_prove_mixed_desc {  /* fourteen 8-byte words, in this order */
+    const uint8_t *p_be;              /* this proof's prime, big-endian */
+    uint64_t p_len;
+    uint64_t sectors;                 /* this proof's S (below 2^32) */
+    uint64_t key_len;                 /* chal_key bytes: 16, 24 or 32 */
+    hb_prove_desc d;                  /* the ten words of hb_prove_desc, same meaning */
+} hb_prove_mixed_desc;
+
+int hb_prove_mixed(hb_ctx *ctx, const hb_prove_mixed_desc *proofs, uint64_t nproofs, uint32_t flags);
+
+/* hb_verify_rhs_many for the proofs of many owners: every proof names its own
+ * prime, `sectors`, state key length and challenge key length.  Replaces an
+ * auditor's loop of hb_verify_rhs over the proofs of several owners
+ * (PySwizzle.py:381-394 per proof): proof i's rhs_out (hb_width(its own p)
+ * bytes) receives exactly the bytes hb_verify_rhs writes for the same
+ * arguments.  Classes (limb count, AES round count), groups and launches
+ * (one PRF launch, one sum launch per group) as in hb_prove_mixed; a proof
+ * whose key_len and chal_key_len have different round counts, or with more
+ * challenge indices than the quad engine places, goes through the single
+ * verify under its own prime inside the same call.  flags must be 0 (anything
+ * else returns HB_EUNSUPPORTED); nproofs == 0 returns HB_OK.  Every
+ * descriptor is checked before any GPU work with hb_verify_rhs's rules and
+ * codes for that proof's own arguments; hb_last_error names the proof and no
+ * result buffer is written. */
+typedef struct hb_verify_mixed_desc { /* fourteen 8-byte words, in this order */
+    const uint8_t *p_be;
+    uint64_t p_len;
+    uint64_t sectors;
+    uint64_t key_len, chal_key_len;   /* f_key / alpha_key bytes; chal_key bytes */
+    hb_verify_desc d;                 /* the nine words of hb_verify_desc, same meaning */
+} hb_verify_mixed_desc;
+
+int hb_verify_rhs_mixed(hb_ctx *ctx, const hb_verify_mixed_desc *proofs, uint64_t nproofs, uint32_t flags);
+
 /* Right-hand side of the cxx extension's verify (shacham_waters_private.cxx:
  * 791-842) for a decrypted state: the same sum as hb_verify_rhs with the cxx
  * prf (cxx/prf.hxx) for index, v, f and alpha, and every block in order when
