@@ -625,6 +625,96 @@ class Swizzle(_Serializable):
         return out
 
     @staticmethod
+    def prove_mixed(items):
+        """b.prove(file, chal, tag) of every (beat, file, chal, tag) of
+        `items`, with any mix of beats -- primes, sector counts, challenge key
+        lengths -- in one batched GPU call (hb_cxx_prove_mixed): the proofs a
+        storage node owes to many owners, each of whom drew their own prime
+        (init, shacham_waters_private.cxx:596-624).  [Proof, ...], exactly
+        what [b.prove(f, c, t) for b, f, c, t in items] returns (:731-789 per
+        item) -- a zero proof for chunks <= 0 -- and
+        HeartbeatError("tag is empty") at the first item a loop would raise it
+        for.  Every item is checked before any GPU work.  Files are read at
+        absolute offsets and their position is restored.  Challenges that
+        prove() would shard over several GPUs go through prove(), and so does
+        a batch of fewer than CXX_PROVE_MANY_MIN items."""
+        items = list(items)
+        out = [None] * len(items)
+        cand = []
+        for i, (beat, file, chal, tag) in enumerate(items):
+            beat._check()
+            if len(tag) == 0:
+                raise HeartbeatError("tag is empty")
+            if int(chal.chunks) <= 0:
+                out[i] = Proof()
+                out[i].mu = [0] * int(beat.sectors)
+                out[i].sigma = 0
+            else:
+                cand.append(i)
+        ndev = len(multi.devices())
+        batch = [i for i in cand
+                 if multi.shard_count(ndev, int(items[i][2].chunks), multi.MIN_SHARD_CHUNKS) == 1]
+        if len(batch) < CXX_PROVE_MANY_MIN:
+            batch = []
+        if batch:
+            res = prove_files_mixed(
+                [(int(items[i][0].prime), int(items[i][0].sectors), items[i][2].key, int(items[i][2].chunks),
+                  int(items[i][2].v_max), items[i][3], items[i][1]) for i in batch])
+            for i, (mu, sigma) in zip(batch, res):
+                out[i] = Proof()
+                out[i].mu, out[i].sigma = mu, sigma
+        for i, (beat, file, chal, tag) in enumerate(items):
+            if out[i] is None:
+                out[i] = beat.prove(file, chal, tag)
+        return out
+
+    @staticmethod
+    def verify_mixed(items):
+        """b.verify(proof, chal, state) of every (beat, proof, chal, state) of
+        `items`, with any mix of beats, in one batched GPU call
+        (hb_cxx_verify_rhs_mixed): an auditor checking the proofs of several
+        owners.  Each state is authenticated and decrypted with its own beat's
+        keys, on a copy.  Exactly what a loop of verify() (:791-842) returns,
+        in order -- None for arguments of the wrong types, False for a state
+        that does not authenticate under its own beat or len(mu) != sectors
+        -- and HeartbeatError("state has no chunks") as the loop would raise
+        it.  Every item is checked before any GPU work.  A batch of fewer than
+        CXX_VERIFY_MANY_MIN items goes through verify()."""
+        items = list(items)
+        out = [None] * len(items)
+        pre = {}
+        for i, (beat, proof, chal, state) in enumerate(items):
+            if not (isinstance(proof, Proof) and isinstance(chal, Challenge) and isinstance(state, State)):
+                continue   # None
+            s = state._copy()   # `state s = s_enc` (:796)
+            if s.encrypted and not s._check_sig_and_decrypt(beat.k_enc, beat.k_mac):
+                out[i] = False
+                continue
+            beat._check()
+            S = int(beat.sectors)
+            mu = list(proof.mu)
+            if len(mu) != S:
+                out[i] = False
+                continue
+            chunks = max(int(chal.chunks), 0)
+            if chunks and int(s.n) <= 0:
+                raise HeartbeatError("state has no chunks")
+            pre[i] = (int(beat.prime), S, _kb(s.f_key), _kb(s.alpha_key), int(s.n), _kb(chal.key), chunks,
+                      int(chal.v_max) if chunks else 1, mu)
+        batch = [i for i, t in pre.items() if len(t[2]) == len(t[3])]
+        if len(batch) < CXX_VERIFY_MANY_MIN:
+            batch = []
+        if batch:
+            rhs = verify_rhs_mixed([pre[i] for i in batch])
+            for i, r in zip(batch, rhs):
+                out[i] = int(items[i][1].sigma) == r
+        for i in pre:
+            if out[i] is None:
+                beat, proof, chal, state = items[i]
+                out[i] = beat.verify(proof, chal, state)
+        return out
+
+    @staticmethod
     def tag_type():
         return Tag
 
@@ -674,7 +764,13 @@ def encode_files(p, sectors, keys, files):
 # profiles/many/cxx_pv_many_rate.json) -- the single cxx calls
 # take none of the fused paths: a prove is a PRF launch, a weighted sum and
 # their synchronisation, a verify up to four PRF launches, a Montgomery pass
-# and a sum -- so every non-empty list takes the batch.
+# and a sum -- so every non-empty list takes the batch.  The static
+# prove_mixed / verify_mixed (hb_cxx_prove_mixed, hb_cxx_verify_rhs_mixed) use
+# the same two constants: one proof through the mixed call is ahead of one
+# single call in all six shapes as well (B's slowest round against A's fastest
+# 1.11x to 1.47x, from 1.9x at two proofs and 2.7x at three: the --proofs 1, 2
+# and 3 rows of scripts/cxx_mixed_many_rate.py,
+# profiles/many/cxx_mixed_many_rate.json).
 CXX_PROVE_MANY_MIN = 1
 CXX_VERIFY_MANY_MIN = 1
 
@@ -702,6 +798,27 @@ def verify_rhs_many(p, sectors, items):
     not spread over several GPUs)."""
     # exactly `sectors` mu values, as the message says
     return _many.verify_rhs_many("hb_cxx_verify_rhs_many", p, sectors, items, exact_mu=True)
+
+
+def prove_files_mixed(items):
+    """Batched GPU prove (hb_cxx_prove_mixed) of the challenges of many owners
+    with the cxx prf: `items` is a list of (p, sectors, chal_key, chunks,
+    v_max, tag, file), each under its own prime, sector count and key length;
+    returns [(mu list, sigma), ...], what hb_prove(HB_PRF_CXX) gives per item
+    (shacham_waters_private.cxx:731-789).  File handling and checks as
+    prove_files.  Runs on multi.primary_context()."""
+    return _many.prove_files_mixed(items, native="hb_cxx_prove_mixed")
+
+
+def verify_rhs_mixed(items):
+    """Batched right-hand sides (hb_cxx_verify_rhs_mixed) of the proofs of
+    many owners with the cxx prf: `items` is a list of (p, sectors, f_key,
+    alpha_key, state_chunks, chal_key, chunks, v_max, mu_list) with decrypted
+    state keys, each under its own prime, sector count and key lengths;
+    returns the list of ints that hb_cxx_verify_rhs gives per item
+    (shacham_waters_private.cxx:791-842).  A proof has exactly `sectors` mu
+    values.  Runs on multi.primary_context()."""
+    return _many.verify_rhs_mixed(items, native="hb_cxx_verify_rhs_mixed", exact_mu=True)
 
 
 # The extension module's path (cxx/Swizzle.hxx:738, imported as

@@ -181,12 +181,13 @@ def verify_rhs_many(native, p, sectors, items, exact_mu):
     return [int.from_bytes(raw[i * w:(i + 1) * w], "big") for i in range(len(keep))]
 
 
-def prove_files_mixed(items):
+def prove_files_mixed(items, native="hb_prove_mixed"):
     """[(mu list, sigma), ...] of `items` = (p, sectors, chal_key, chunks,
-    v_max, tag, file) in one hb_prove_mixed call: every item under its own
-    prime, sector count and key length (the proofs of many owners).  File
-    handling as prove_files: every file read whole from its start, its
-    position left where it was."""
+    v_max, tag, file) in one call of `native` (hb_prove_mixed, or
+    hb_cxx_prove_mixed for the cxx Swizzle): every item under its own prime,
+    sector count and key length (the proofs of many owners).  File handling as
+    prove_files: every file read whole from its start, its position left where
+    it was."""
     keep = []
     for p, S, ck, chunks, v_max, tag, file in items:
         p, S = int(p), int(S)
@@ -222,7 +223,7 @@ def prove_files_mixed(items):
             d.sigma_out = base + offs[i] + S * w
         ctx = multi.primary_context()
         with ctx.lock:
-            ctx.check(_native.lib().hb_prove_mixed(ctx.h, descs, n, 0))
+            ctx.check(getattr(_native.lib(), native)(ctx.h, descs, n, 0))
     finally:
         for fb in fbs:
             fb.restore()
@@ -236,18 +237,22 @@ def prove_files_mixed(items):
     return res
 
 
-def verify_rhs_mixed(items):
+def verify_rhs_mixed(items, native="hb_verify_rhs_mixed", exact_mu=False):
     """The right-hand sides (ints) of `items` = (p, sectors, f_key, alpha_key,
     state_chunks, chal_key, chunks, v_max, mu_list) with decrypted state keys
-    in one hb_verify_rhs_mixed call: every item under its own prime, sector
-    count and key lengths.  A proof may have more than `sectors` mu values;
-    the first `sectors` count."""
+    in one call of `native` (hb_verify_rhs_mixed, or hb_cxx_verify_rhs_mixed
+    for the cxx Swizzle): every item under its own prime, sector count and key
+    lengths.  exact_mu (Swizzle.verify_rhs_mixed): a proof has exactly
+    `sectors` mu values.  Without it a proof may have more, and the first
+    `sectors` count."""
     keep = []
     for p, S, fk, ak, nstate, ck, chunks, v_max, mu in items:
         p, S = int(p), int(S)
         _check(p, S)
         w = _native.width_of(p)
         mu = list(mu)
+        if exact_mu and len(mu) != S:
+            raise HeartbeatError("proof has %d mu values, not %d" % (len(mu), S))
         if len(mu) < S:
             raise HeartbeatError("proof has fewer than %d mu values" % S)
         fk, ak = _kb(fk), _kb(ak)
@@ -277,6 +282,6 @@ def verify_rhs_mixed(items):
         d.rhs_out = base + offs[i]
     ctx = multi.primary_context()
     with ctx.lock:
-        ctx.check(_native.lib().hb_verify_rhs_mixed(ctx.h, descs, n, 0))
+        ctx.check(getattr(_native.lib(), native)(ctx.h, descs, n, 0))
     raw = out.raw
     return [int.from_bytes(raw[offs[i]:offs[i] + _native.width_of(keep[i][0])], "big") for i in range(n)]

@@ -104,6 +104,8 @@ SIGNATURES = [
                                  _c.c_uint64, _c.c_uint32]),
     ("hb_prove_mixed", _c.c_int, [_P, _c.POINTER(ProveMixedDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_verify_rhs_mixed", _c.c_int, [_P, _c.POINTER(VerifyMixedDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_cxx_prove_mixed", _c.c_int, [_P, _c.POINTER(ProveMixedDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_cxx_verify_rhs_mixed", _c.c_int, [_P, _c.POINTER(VerifyMixedDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_verify_rhs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t,
                                  _c.c_uint64, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_size_t,
                                  _B, _P]),

@@ -34,7 +34,7 @@ inline uint64_t hb_test_cap(const char *v) {
 // of 16: first the uploaded ones, then end_upload(), then the device-only and
 // downloaded ones.  A section of no bytes takes no room.
 struct HbArena {
-    enum { kMaxSections = 12 };
+    enum { kMaxSections = 16 };
     uint64_t off[kMaxSections];
     uint32_t n = 0;
     uint64_t up_bytes = 0;   // [0, up_bytes): one H2D copy

@@ -34,8 +34,19 @@
 #include "hb_batch.hpp"
 #include "hb_cpv_args.hpp"
 
-template <int NL, int NR>
-__global__ __launch_bounds__(HB_ENGINE_WG) void hb_cpv_prf_kernel(CpvPrfArgs<NL> A) {
+// Where an item's alpha values land in A.av, in slots of NL limbs: with one S
+// for the batch, item * S.  (hb_cmixed.hpp has the other one: each proof's
+// own first slot, read from the item's entry where it is used.)
+struct CpvAlphaShared {
+    u32 S;
+    template <int NL>
+    __device__ __forceinline__ u64 operator()(const CpvPrfArgs<NL> &, u32 item) const { return (u64)item * S; }
+};
+
+// The PRF launch's body, shared by hb_cpv_prf_kernel and the cxx mixed-owner
+// batch's hb_cmixed_prf_kernel: they differ in AlphaBase alone.
+template <int NL, int NR, class AlphaBase>
+__device__ __forceinline__ void hb_cpv_prf_body(const CpvPrfArgs<NL> &A, const AlphaBase &alpha_base) {
     __shared__ __attribute__((aligned(16))) u32 lds[HB_LDS_WORDS];
     hb_fill_lds(lds, A.t0);
     const LaneTab L = hb_lane_tab(lds);
@@ -99,7 +110,7 @@ __global__ __launch_bounds__(HB_ENGINE_WG) void hb_cpv_prf_kernel(CpvPrfArgs<NL>
             hb_load_uniform(A.prf, A.stride * item + slot, P);
             u32 *dst = kind == HB_CB_V      ? A.vv + (V.obase + i) * NL
                        : kind == HB_CB_IDXF ? A.fv + (V.obase + i) * NL
-                                            : A.av + ((u64)item * A.S + i) * NL;
+                                            : A.av + (alpha_base(A, item) + i) * NL;
             u32 out[NL];
             hb_zero_sr(sr);   // resynchronised per evaluate (prf.hxx:132)
             hb_sha256_le32((u32)x, dig);
@@ -119,6 +130,11 @@ __global__ __launch_bounds__(HB_ENGINE_WG) void hb_cpv_prf_kernel(CpvPrfArgs<NL>
         for (int off = 32; off > 0; off >>= 1) tries += __shfl_xor(tries, off);
         if (hb_lane_id() == 0 && tries) atomicAdd(A.queue + kind * HB_QSLOT + 1, (unsigned long long)tries);
     }
+}
+
+template <int NL, int NR>
+__global__ __launch_bounds__(HB_ENGINE_WG) void hb_cpv_prf_kernel(CpvPrfArgs<NL> A) {
+    hb_cpv_prf_body<NL, NR>(A, CpvAlphaShared{A.S});
 }
 
 // One (file, column) result per workgroup, hb_pbatch_sum_kernel's sum with the

@@ -6,7 +6,9 @@
 // prefix sums, the workgroup tables themselves, and the cache of Montgomery
 // constants per distinct prime.  Pure host code: no HIP, no context, so that a
 // stand-alone program can walk it (tests/mixed_host/host_main.cpp, built with
-// AddressSanitizer and UBSan).
+// AddressSanitizer and UBSan).  The cxx Swizzle's mixed-owner batches
+// (hb_cxx_prove_mixed, hb_cxx_verify_rhs_mixed) share all of it and add their
+// two arena layouts and costs below (tests/cxx_mixed_host/host_main.cpp).
 #pragma once
 #include <map>
 #include <string>
@@ -133,6 +135,70 @@ inline HbArena hb_mverify_arena(const HbBatchSizes &z, uint64_t rec, uint64_t np
 inline uint64_t hb_mverify_cost(const HbBatchSizes &z, uint64_t rec, uint64_t nj, uint64_t n, uint64_t S) {
     return z.prf2 + 3 * z.prf + z.vproof + rec + nj * HB_JOB_BYTES + (2 * n + 2 * S + 1) * z.limbs;
 }
+
+// hb_cxx_prove_mixed (z.item: CpvItem, the PRF launch's entry; z.pproof:
+// PbProof, the conversion pass's and the sum launch's):
+//     [index schedules | v schedules | items | proofs | records | sum workgroups | conversion workgroups | wave-jobs |
+//      host files and tags] (uploaded) [idx | v | results | status]
+// np proofs of `terms` EFFECTIVE challenge indices and `cols` result columns in
+// all, nj wave-jobs of HB_CB_JOB evaluations.  Results and status words are
+// adjacent: one D2H copy of [off[HB_CMP_RES], total).
+enum { HB_CMP_PIDX, HB_CMP_PV, HB_CMP_ITEMS, HB_CMP_PROOFS, HB_CMP_RECS, HB_CMP_SUMWG, HB_CMP_MONTWG, HB_CMP_JOBS,
+       HB_CMP_DATA, HB_CMP_IDX, HB_CMP_VV, HB_CMP_RES, HB_CMP_STATUS, HB_CMP_SECTIONS };
+inline HbArena hb_cmprove_arena(const HbBatchSizes &z, uint64_t rec, uint64_t np, uint64_t nj, uint64_t cols, uint64_t nmwg,
+                                uint64_t up_files, uint64_t terms) {
+    HbArena L;
+    L.add(np * z.prf2);
+    L.add(np * z.prf);
+    L.add(np * z.item);
+    L.add(np * z.pproof);
+    L.add(np * rec);
+    L.add(cols * HB_MXWG_BYTES);
+    L.add(nmwg * HB_MXWG_BYTES);
+    L.add(nj * HB_JOB_BYTES);
+    L.add(up_files);
+    L.end_upload();
+    L.add(terms * 8);
+    L.add(terms * z.limbs);
+    L.add(cols * z.limbs);
+    L.add(np * 4);
+    return L;
+}
+// scratch bytes of one proof of n effective challenge indices, S sectors and nj
+// wave-jobs (exact; the section padding is the arena's: at most 16 per section)
+inline uint64_t hb_cmprove_cost(const HbBatchSizes &z, uint64_t rec, uint64_t nj, uint64_t n, uint64_t S, uint64_t up_files) {
+    return z.prf2 + z.prf + z.item + z.pproof + rec + (S + 1) * HB_MXWG_BYTES + hb_mixed_mont_wg_count(n) * HB_MXWG_BYTES +
+           nj * HB_JOB_BYTES + up_files + n * (8 + z.limbs) + (S + 1) * z.limbs + 4;
+}
+
+// hb_cxx_verify_rhs_mixed:
+//     [index schedules | v, F, alpha schedules | items | proofs | records | wave-jobs | mu] (uploaded)
+//     [v | F | alpha | results]
+// np proofs of `terms` effective challenge indices and `slots` alpha / mu slots in all.
+enum { HB_CMV_PIDX, HB_CMV_PRF, HB_CMV_ITEMS, HB_CMV_PROOFS, HB_CMV_RECS, HB_CMV_JOBS, HB_CMV_MU, HB_CMV_VV, HB_CMV_FV,
+       HB_CMV_AV, HB_CMV_RES, HB_CMV_SECTIONS };
+inline HbArena hb_cmverify_arena(const HbBatchSizes &z, uint64_t rec, uint64_t np, uint64_t nj, uint64_t terms, uint64_t slots) {
+    HbArena L;
+    L.add(np * z.prf2);
+    L.add(3 * np * z.prf);
+    L.add(np * z.item);
+    L.add(np * z.vproof);
+    L.add(np * rec);
+    L.add(nj * HB_JOB_BYTES);
+    L.add(slots * z.limbs);
+    L.end_upload();
+    L.add(terms * z.limbs);
+    L.add(terms * z.limbs);
+    L.add(slots * z.limbs);
+    L.add(np * z.limbs);
+    return L;
+}
+inline uint64_t hb_cmverify_cost(const HbBatchSizes &z, uint64_t rec, uint64_t nj, uint64_t n, uint64_t S) {
+    return z.prf2 + 3 * z.prf + z.item + z.vproof + rec + nj * HB_JOB_BYTES + (2 * n + 2 * S + 1) * z.limbs;
+}
+
+// wave-jobs of n evaluations of one kind of a cxx batch (hb_cbatch_jobs)
+inline uint64_t hb_cm_jobs(uint64_t n) { return (n + HB_CB_JOB - 1) / HB_CB_JOB; }
 
 // ------------------------------------------------------------------ distinct primes
 // The Montgomery constants of a prime (R^2 mod p by 64 NL modular doublings,

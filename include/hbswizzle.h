@@ -578,6 +578,54 @@ int hb_cxx_verify_rhs_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint3
                            size_t key_len, size_t chal_key_len,
                            const hb_verify_desc *proofs, uint64_t nproofs, uint32_t flags);
 
+/* hb_cxx_prove_many for the proofs of many owners: every proof names its own
+ * prime, `sectors` and challenge key length.  Every cxx Swizzle draws its own
+ * prime (init, cxx/shacham_waters_private.cxx:596-624) and hands it to the
+ * storage node with the public beat, so a node that answers an audit period's
+ * challenges for several owners has one prime per owner.  Replaces that node's
+ * loop over cxx/shacham_waters_private.cxx:731-789 with the prf of
+ * cxx/prf.hxx:125-176 (one hb_prove with HB_PRF_CXX per proof): proof i's
+ * mu_out (its own sectors * hb_width(its own p) bytes) and sigma_out receive
+ * exactly the bytes hb_prove(..., flags | HB_PRF_CXX, ...) writes for that
+ * proof's own arguments, check_all when chunks >= ntags and the (unsigned
+ * int) sector offsets under that proof's own sectors * sector size included.
+ * Takes hb_prove_mixed_desc unchanged.  Classes (limb count, AES round count)
+ * as in hb_prove_mixed; a class is grouped and run as hb_cxx_prove_many runs a
+ * batch -- per group one H2D copy, one PRF launch, one conversion pass, one
+ * sum launch, one D2H copy -- with each proof's modulus, geometry and result
+ * columns in a per-proof device record; Montgomery constants once per
+ * distinct prime.  A proof goes through the single cxx prove under its own
+ * prime and `sectors` inside the same call, with identical results, when
+ * ByteCount(its p) or ByteCount(its v_max) is not a multiple of 16, with host
+ * data and device tags, with a host file above max(2 n C, 8 MiB) (n: its
+ * effective chunks, C: its own), or when it alone exceeds the runtime's
+ * scratch cap.  flags: HB_DATA_ON_DEVICE and/or HB_TAGS_ON_DEVICE; anything
+ * else returns HB_EUNSUPPORTED.  nproofs == 0 returns HB_OK; a proof with
+ * chunks == 0 gets zero mu and sigma and no GPU work.  Every descriptor is
+ * checked before any GPU work with hb_prove(HB_PRF_CXX)'s rules and codes for
+ * that proof's own prime, sectors, key length and arguments (ntags >= 2^32:
+ * HB_EUNSUPPORTED); hb_last_error names the proof ("proof 3: ...") and no
+ * result buffer is written.  Parity unpinned, as every cxx entry point. */
+int hb_cxx_prove_mixed(hb_ctx *ctx, const hb_prove_mixed_desc *proofs, uint64_t nproofs, uint32_t flags);
+
+/* hb_cxx_verify_rhs_many for the proofs of many owners: every proof names its
+ * own prime, `sectors`, state key length and challenge key length.  Replaces
+ * an auditor's loop over cxx/shacham_waters_private.cxx:791-842 with the prf
+ * of cxx/prf.hxx:125-176 (one hb_cxx_verify_rhs per proof): proof i's rhs_out
+ * (hb_width(its own p) bytes) receives exactly the bytes hb_cxx_verify_rhs
+ * writes for the same arguments.  Takes hb_verify_mixed_desc unchanged.
+ * Classes, groups and launches (one PRF launch, one sum launch per group) as
+ * in hb_cxx_prove_mixed; a proof whose key_len and chal_key_len have different
+ * AES round counts, whose prime's or v_max's ByteCount is not a multiple of
+ * 16, or which alone exceeds the scratch cap goes through hb_cxx_verify_rhs's
+ * path under its own prime inside the same call.  flags must be 0 (anything
+ * else returns HB_EUNSUPPORTED); nproofs == 0 returns HB_OK.  Every
+ * descriptor is checked before any GPU work with hb_cxx_verify_rhs's rules
+ * and codes for that proof's own arguments (state_chunks >= 2^32:
+ * HB_EUNSUPPORTED); hb_last_error names the proof and no result buffer is
+ * written. */
+int hb_cxx_verify_rhs_mixed(hb_ctx *ctx, const hb_verify_mixed_desc *proofs, uint64_t nproofs, uint32_t flags);
+
 /* Host AES-CFB8 (segment 8, any 16-byte IV) for PySwizzle State
  * encrypt/decrypt (PySwizzle.py:162-195): 64 bytes per call, not a hot path.
  * encrypt = 1 encrypts, 0 decrypts. */
