@@ -303,6 +303,34 @@ class PySwizzle(object):
             out.append((tag, state))
         return out
 
+    @staticmethod
+    def encode_mixed(items):
+        """b.encode(file) of every (beat, file) of `items`, with any mix of
+        beats -- primes, sector counts -- in one batched GPU call
+        (hb_encode_mixed): a process that keeps one beat per owner, contract or
+        farmer, each with its own prime (PySwizzle.py:250-251), and tags one
+        file for each.  [(Tag, State), ...], exactly what
+        [b.encode(f) for b, f in items] returns (PySwizzle.py:279-311 per
+        item): fresh random keys per file, each state encrypted under its own
+        beat's key, each file read from its current position to EOF and left
+        there.  Every beat is checked before any file is read, and the
+        HeartbeatError is that of the first item a loop would raise it for.  A
+        batch of fewer than ENCODE_MIXED_MIN items goes through encode()."""
+        items = list(items)
+        for beat, _ in items:
+            beat._check()
+        if len(items) < ENCODE_MIXED_MIN:
+            return [beat.encode(file) for beat, file in items]
+        states = [State(_random_bytes(32), _random_bytes(32)) for _ in items]
+        res = encode_files_mixed([(int(beat.prime), int(beat.sectors), s.f_key, s.alpha_key, file)
+                                  for (beat, file), s in zip(items, states)])
+        out = []
+        for (beat, _), state, (tag, nblocks) in zip(items, states, res):
+            state.chunks = nblocks
+            state.encrypt(beat.key)
+            out.append((tag, state))
+        return out
+
     def gen_challenge(self, state):
         """Challenge every block once on average (chunks = #blocks, v_max = p)."""
         state.decrypt(self.key)
@@ -599,6 +627,29 @@ def encode_files(p, sectors, keys, files):
     multi.primary_context() (a batch is not spread over several GPUs)."""
     # a file is opened as its descriptor is filled
     return _many.encode_files("hb_encode_many", Tag, p, sectors, keys, files, open_first=False)
+
+
+# Fewest files PySwizzle.encode_mixed sends through hb_encode_mixed; below it
+# the items go through encode() one by one: the smallest file count at which
+# the mixed call's slowest round beats the loop's fastest, device-resident and
+# from host memory.  One file through the group's three launches only ties
+# with the single encode when the bytes are on the device (1024-bit, S = 10,
+# 1 MiB: 0.82-0.84 against 0.83-0.86 ms; from host memory 0.90-0.97 against
+# 0.98-1.07), two files win in both (0.81-0.95 against 1.39-1.48 ms;
+# 0.90-1.03 against 1.62-1.72), three by 2.6x: the --files 1, 2 and 3 rows of
+# scripts/encode_mixed_rate.py, profiles/many/encode_mixed_rate.json,
+# DESIGN.md 5.3i.
+ENCODE_MIXED_MIN = 2
+
+
+def encode_files_mixed(items):
+    """Batched GPU encode (hb_encode_mixed) of the files of many owners:
+    `items` is a list of (p, sectors, f_key, alpha_key, file), every file under
+    its own prime, sector count and key length; returns
+    [(Tag, number of blocks), ...], what encode_file gives per item.  Each file
+    is read from its current position to EOF and left there.  Runs on
+    multi.primary_context() (a batch is not spread over several GPUs)."""
+    return _many.encode_files_mixed(items, "hb_encode_mixed", Tag, open_first=False)
 
 
 # Fewest proofs PySwizzle.prove_many sends through hb_prove_many; below it the

@@ -468,6 +468,39 @@ class Swizzle(_Serializable):
             out.append((tag, state))
         return out
 
+    @staticmethod
+    def encode_mixed(items):
+        """b.encode(file) of every (beat, file) of `items`, with any mix of
+        beats -- primes, sector counts -- in one batched GPU call
+        (hb_cxx_encode_mixed): a process that keeps one beat per owner, each
+        with its own prime (init, shacham_waters_private.cxx:596-624), and tags
+        one file for each.  [(Tag, State), ...], exactly what
+        [b.encode(f) for b, f in items] returns (:638-702 per item): fresh keys
+        per file, each state encrypted and signed under its own beat's keys,
+        each file read from its position to EOF and left there.  Every beat is
+        checked before any file is read, and the HeartbeatError is that of the
+        first item a loop would raise it for.  A batch of fewer than
+        CXX_ENCODE_MIXED_MIN items goes through encode()."""
+        items = list(items)
+        for beat, _ in items:
+            beat._check()
+        if len(items) < CXX_ENCODE_MIXED_MIN:
+            return [beat.encode(file) for beat, file in items]
+        states = []
+        for _ in items:
+            state = State()
+            state.f_key = _random_bytes(KEY_SIZE)
+            state.alpha_key = _random_bytes(KEY_SIZE)
+            states.append(state)
+        res = encode_files_mixed([(beat.prime, beat.sectors, s.f_key, s.alpha_key, file)
+                                  for (beat, file), s in zip(items, states)])
+        out = []
+        for (beat, _), state, (tag, nblocks) in zip(items, states, res):
+            state.n = nblocks
+            state.encrypt(beat.k_enc, beat.k_mac)
+            out.append((tag, state))
+        return out
+
     def gen_challenge(self, state):
         """l = (unsigned int)(check_fraction * n) indices, v limit p (:704-729)."""
         s = state._copy()   # `state s = s_enc` (:706)
@@ -752,6 +785,30 @@ def encode_files(p, sectors, keys, files):
     Runs on multi.primary_context() (a batch is not spread over several
     GPUs)."""
     return _many.encode_files("hb_cxx_encode_many", Tag, p, sectors, keys, files, open_first=True)
+
+
+# Fewest files Swizzle.encode_mixed sends through hb_cxx_encode_mixed; below it
+# the items go through encode() one by one: the smallest file count at which
+# the mixed call's slowest round beats the loop's fastest.  Already one file is
+# ahead (1024-bit, S = 10, 1 MiB: 0.22-0.28 against 0.32-0.35 ms
+# device-resident, 0.29-0.36 against 0.48-0.51 from host memory; 2.7x and 2.5x
+# at two files, 3.7x and 3.2x at three: the --files 1, 2 and 3 rows of
+# scripts/encode_mixed_rate.py --cxx, profiles/many/cxx_encode_mixed_rate.json,
+# DESIGN.md 5.3i), as with CXX_ENCODE_MANY_MIN, so every non-empty list takes
+# the mixed call.
+CXX_ENCODE_MIXED_MIN = 1
+
+
+def encode_files_mixed(items):
+    """Batched GPU encode (hb_cxx_encode_mixed) of the files of many owners
+    with the cxx prf: `items` is a list of (p, sectors, f_key, alpha_key,
+    file), every file under its own prime, sector count and key length; returns
+    [(Tag, number of blocks), ...], what hb_encode(HB_PRF_CXX) gives per item
+    (shacham_waters_private.cxx:638-702).  File handling as encode_files:
+    every file is opened before any GPU work; if one cannot be read, the files
+    before it are left at EOF as the loop leaves them and its error is raised.
+    Runs on multi.primary_context()."""
+    return _many.encode_files_mixed(items, "hb_cxx_encode_mixed", Tag, open_first=True)
 
 
 # Fewest proofs Swizzle.prove_many sends through hb_cxx_prove_many, and

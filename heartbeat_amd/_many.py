@@ -80,6 +80,63 @@ def encode_files(native, Tag, p, sectors, keys, files, open_first):
     return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks in outs]
 
 
+def encode_files_mixed(items, native, Tag, open_first):
+    """[(Tag, number of blocks), ...] of `items` = (p, sectors, f_key,
+    alpha_key, file) in one call of `native` (hb_encode_mixed, or
+    hb_cxx_encode_mixed for the cxx Swizzle): every file under its own prime,
+    sector count and key length (the files of many owners).  File handling as
+    encode_files: each file from its current position to EOF and left there,
+    and open_first as there."""
+    keep, files = [], []
+    for p, S, fk, ak, file in items:
+        p, S = int(p), int(S)
+        _check(p, S)
+        fk, ak = _kb(fk), _kb(ak)
+        if len(fk) != len(ak):
+            raise HeartbeatError("f_key and alpha_key must have the same length")
+        keep.append((p, S, _native.be(p), fk, ak))
+        files.append(file)
+    if not keep:
+        return []
+    n = len(keep)
+    fbs, outs = [], []
+    try:
+        descs = (_native.EncodeMixedDesc * n)()
+        if open_first:
+            try:
+                for file in files:
+                    fbs.append(FileBuffer(file))
+            except BaseException:
+                for fb in fbs:
+                    fb.consume()
+                raise
+        for i, (p, S, pb, fk, ak) in enumerate(keep):
+            if not open_first:
+                fbs.append(FileBuffer(files[i]))
+            fb = fbs[i]
+            w = _native.width_of(p)
+            nblocks = fb.len // ((p.bit_length() // 8) * S) + 1
+            # the tags land in the array the Tag keeps
+            out = np.empty(nblocks * w, dtype=np.uint8)
+            outs.append((out, nblocks, w))
+            d = descs[i]
+            d.p_be, d.p_len, d.sectors, d.key_len = pb, len(pb), S, len(fk)
+            d.f_key, d.alpha_key = fk, ak
+            d.data = fb.addr
+            d.len = fb.len
+            d.tags = out.ctypes.data
+        ctx = multi.primary_context()
+        tries = ctypes.c_uint64()
+        with ctx.lock:
+            ctx.check(getattr(_native.lib(), native)(ctx.h, descs, n, 0, ctypes.byref(tries)))
+        for fb in fbs:
+            fb.consume()
+    finally:
+        for fb in fbs:
+            fb.close()
+    return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks, w in outs]
+
+
 def prove_files(native, p, sectors, items):
     """[(mu list, sigma), ...] of `items` = (chal_key, chunks, v_max, tag,
     file).  Every file is read whole, from its start (absolute offsets, as the

@@ -66,6 +66,13 @@ class ProveMixedDesc(ctypes.Structure):
                 ("sectors", ctypes.c_uint64), ("key_len", ctypes.c_uint64)] + ProveDesc._fields_
 
 
+class EncodeMixedDesc(ctypes.Structure):
+    """hb_encode_mixed_desc (hbswizzle.h): one file of an hb_encode_mixed call,
+    under its own prime, sector count and key length; then hb_file_desc's words."""
+    _fields_ = [("p_be", ctypes.c_char_p), ("p_len", ctypes.c_uint64),
+                ("sectors", ctypes.c_uint64), ("key_len", ctypes.c_uint64)] + FileDesc._fields_
+
+
 class VerifyMixedDesc(ctypes.Structure):
     """hb_verify_mixed_desc (hbswizzle.h): one proof of an hb_verify_rhs_mixed
     call, under its own prime, sector count and key lengths; then hb_verify_desc's words."""
@@ -94,6 +101,10 @@ SIGNATURES = [
                                   _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_cxx_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
                                       _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,
+                                   _c.POINTER(_c.c_uint64)]),
+    ("hb_cxx_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,
+                                       _c.POINTER(_c.c_uint64)]),
     ("hb_block_count", _c.c_uint64, [_B, _c.c_size_t, _c.c_uint32, _c.c_uint64]),
     ("hb_prove", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _c.c_size_t, _c.c_uint64, _B,
                             _c.c_size_t, _P, _c.c_uint64, _P, _c.c_uint64, _c.c_uint32, _P, _P]),

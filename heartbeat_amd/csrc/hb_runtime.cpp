@@ -33,9 +33,11 @@
 #include "hb_cpv_args.hpp"
 #include "hb_mixed_args.hpp"
 #include "hb_cmixed_args.hpp"
+#include "hb_emixed_args.hpp"
 #include "hb_bignum_host.hpp"
 #include "hb_batch_host.hpp"
 #include "hb_mixed_host.hpp"
+#include "hb_emixed_host.hpp"
 
 using namespace hbhost;
 
@@ -78,6 +80,11 @@ template <int NL> hipError_t hb_launch_vmixed_sum(const VmSumArgs<NL> &, u32, hi
 // hb_kern_cmixed.hip / hb_kern_cmixed64.hip
 template <int NL> hipError_t hb_launch_cmixed_sum(const CmSumArgs<NL> &, u32, hipStream_t);
 template <int NL> hipError_t hb_launch_cmixed_prf(const CpvPrfArgs<NL> &, int, int, hipStream_t);
+// hb_kern_emixed.hip / hb_kern_emixed64.hip
+template <int NL> hipError_t hb_launch_emixed_prf(const EmPrfArgs<NL> &, int, int, hipStream_t);
+template <int NL> hipError_t hb_launch_cemixed_prf(const CemPrfArgs<NL> &, int, int, hipStream_t);
+template <int NL> u32 hb_emixed_mac_threads();
+template <int NL> hipError_t hb_launch_emixed_mac(const EmMacArgs<NL> &, u32, u32, hipStream_t);
 
 namespace {
 
@@ -4008,6 +4015,219 @@ int cxx_verify_mixed_impl(hb_ctx *c, const hb_verify_mixed_desc *descs, const st
     });
 }
 
+// ------------------------------------------------------------------ encode, many owners
+// hb_encode_mixed and hb_cxx_encode_mixed (cxx): hb_encode_many and
+// hb_cxx_encode_many for files that each name their own prime, sector count
+// and key length.  The entry point checks every descriptor, looks every prime
+// up in the call's cache (HbPrimeCache) and splits the files into classes
+// (hb_mixed_partition); a class is planned here as the one-prime call plans
+// its files -- same caps, same bound on a batched file's blocks, same queue
+// order -- with what that call keeps in the kernel arguments (ModP, C, ss, S,
+// tw) and the file's first alpha slot in one more uploaded section of per-file
+// records (MxRec), each file's schedules under its own range, and the
+// workgroup tables of the MAC launch and the conversion pass built from each
+// file's own S (hb_emixed_host.hpp).  Both PRF kernels store alpha raw;
+// hb_mixed_mont_kernel converts the group's slots under each file's modulus.
+// Launches per group: PRF, conversion and a MAC launch per shape that has a
+// workgroup (hb_emixed.hpp): 3, with files of both shapes 4, a cxx group
+// without a block that reads a sector 2.  last_launches accumulates over the groups of every
+// class and the single encodes of the files that fall through.
+static_assert(sizeof(HbEmWg) == sizeof(BatchMacWg) && sizeof(HbEmWg) == HB_EMWG_BYTES &&
+                  sizeof(HbEmJob) == sizeof(BatchWaveJob) && sizeof(HbEmJob) == HB_JOB_BYTES,
+              "the tables are the host header's");
+
+template <int NL>
+int encode_mixed_impl(hb_ctx *c, const hb_encode_mixed_desc *descs, const std::vector<u64> &cls, int nr, u32 flags, bool cxx,
+                      const MixedCall &MC, u64 &tries) {
+    const HbBatchSizes z = batch_sizes<NL>();
+    const u64 rec = sizeof(MxRec<NL>);
+    const u32 T = hb_emixed_mac_threads<NL>();
+    const bool data_dev = (flags & HB_DATA_ON_DEVICE) != 0, tags_dev = (flags & HB_TAGS_ON_DEVICE) != 0;
+    const size_t key_len = nr == 10 ? 16 : nr == 12 ? 24 : 32;
+    auto shape_of = [&](u64 i) {
+        const u32 S = (u32)descs[i].sectors;
+        return EncodeShape{(u64)MC.pi[(size_t)i].ss * S, S, hb_em_bpw(T, S), data_dev, tags_dev};
+    };
+    // blocks with a MAC workgroup (cxx: those with a sector read, hb_cbatch_args.hpp)
+    auto mac_blocks_of = [&](u64 i) {
+        const EncodeShape E = shape_of(i);
+        const u64 len = descs[i].d.len;
+        return cxx ? len / E.C + (len % E.C ? 1 : 0) : E.blocks_of(descs[i].d);
+    };
+    auto jobs_of = [&](u64 nb, u64 S) { return cxx ? hb_cm_jobs(nb) + hb_cm_jobs(S) : hb_em_job_count(S, nb); };
+    // which files batch: the files hb_encode_many batches, unless one alone
+    // passes the scratch cap (which also bounds the records' 32-bit slot0)
+    const u64 mid_max = (NL <= 8 ? 17ull : 16ull) * 256ull * (u64)c->num_cus;
+    const u64 cap_blocks = hb_test_cap(sw_env(c, "HB_TEST_BATCH_BLOCKS"));
+    const u64 bound = cap_blocks < mid_max ? cap_blocks : mid_max;
+    const u64 ncls = cls.size();
+    std::vector<HbCbItemReq> req((size_t)ncls);
+    for (u64 k = 0; k < ncls; ++k) {
+        const u64 i = cls[k];
+        const EncodeShape E = shape_of(i);
+        const PrimeInfo &pi = MC.pi[(size_t)i];
+        const u64 nb = E.blocks_of(descs[i].d);
+        HbCbItemReq &R = req[(size_t)k];
+        R = HbCbItemReq{};
+        R.n[HB_CB_F] = nb;
+        R.n[HB_CB_ALPHA] = E.S;
+        R.aes[HB_CB_F] = R.aes[HB_CB_ALPHA] = pi.tw / 16;
+        R.bytes = hb_em_cost(z, rec, jobs_of(nb, E.S), E.wgs_of(mac_blocks_of(i)), E.data_up(descs[i].d), nb, E.S,
+                             E.tags_up(descs[i].d, pi));
+        R.units = R.bytes <= HB_BATCH_BYTES ? nb : ~0ull;   // over any bound: the single call
+    }
+    const HbCbPlan plan = cxx ? hb_cbatch_plan(req.data(), ncls, bound, cap_blocks, HB_BATCH_BYTES)
+                              : hb_batch_groups(req.data(), ncls, bound, cap_blocks, HB_BATCH_BYTES);
+
+    auto run_group = [&](const HbCbGroup &G) -> int {
+        const u64 nf = G.nitems;
+        const u64 *g = plan.order.data() + G.item0;   // positions in cls
+        std::vector<u32> Sv((size_t)nf);
+        std::vector<u64> nbv((size_t)nf), mbv((size_t)nf);
+        u64 dbytes = 0, tbytes = 0;
+        for (u64 f = 0; f < nf; ++f) {
+            const u64 i = cls[g[f]];
+            const EncodeShape E = shape_of(i);
+            Sv[(size_t)f] = E.S;
+            nbv[(size_t)f] = E.blocks_of(descs[i].d);
+            mbv[(size_t)f] = mac_blocks_of(i);
+            dbytes += E.data_up(descs[i].d);
+            tbytes += E.tags_up(descs[i].d, MC.pi[(size_t)i]);
+        }
+        std::vector<u64> slot0, fbase;
+        const u64 slots = hb_mixed_prefix(Sv.data(), nf, 0, slot0);
+        const u64 blocks = hb_em_fbases(nbv.data(), nf, fbase);
+        const u64 nj = cxx ? G.njobs : hb_em_jobs(Sv.data(), nbv.data(), nf, nullptr);
+        u64 nsplit = 0, nsplit2 = 0;
+        const u64 nwg = hb_em_mac_wgs(Sv.data(), mbv.data(), nf, T, nullptr, &nsplit);
+        const u64 nmwg = hb_mixed_mont_wgs(Sv.data(), nf, nullptr);
+        if (blocks != G.units) return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        // arena: [prf | files | records | slot ranges | jobs | wgs | conversion wgs | host files] (uploaded) [F | alpha | tags]
+        const HbArena L = hb_em_arena(z, rec, nf, nj, nwg, nmwg, dbytes, blocks, slots, tbytes);
+        if (int rc = group_arenas(c, L, HB_EMX_TAGS)) return rc;
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        PrfParams<NL> *hprf = L.at<PrfParams<NL>>(host, HB_EMX_PRF);
+        BatchFile *hfiles = L.at<BatchFile>(host, HB_EMX_FILES);
+        MxRec<NL> *hrecs = L.at<MxRec<NL>>(host, HB_EMX_RECS);
+        PbProof *hslots = L.at<PbProof>(host, HB_EMX_SLOTS);
+        u64 doff = L.off[HB_EMX_DATA], toff = L.off[HB_EMX_TAGS];
+        RangeCache<NL> P0;   // rebuilt when the prime differs from the last file's
+        for (u64 f = 0; f < nf; ++f) {
+            const u64 i = cls[g[f]];
+            const hb_encode_mixed_desc &X = descs[i];
+            const hb_file_desc &D = X.d;
+            const PrimeInfo &pi = MC.pi[(size_t)i];
+            const EncodeShape E = shape_of(i);
+            if (!P0.get(D.f_key, key_len, X.p_be, (size_t)X.p_len) ||
+                !schedule<NL>(P0.tmpl, D.f_key, key_len, nr, hprf[2 * f]) ||
+                !schedule<NL>(P0.tmpl, D.alpha_key, key_len, nr, hprf[2 * f + 1]))
+                return fail(c, HB_EINVAL, "invalid key");
+            BatchFile &F = hfiles[f];
+            memset(&F, 0, sizeof F);
+            F.data = stage_in(data_dev, D.data, D.len, host, dev, doff);
+            F.len = D.len;
+            F.tags = D.tags;
+            if (!tags_dev) {
+                F.tags = dev + toff;
+                toff += E.tags_up(D, pi);
+            }
+            F.fbase = fbase[(size_t)f];
+            F.nblocks = (u32)mbv[(size_t)f];
+            // per file, with THIS file's ss, tw and C
+            F.flags = (full16(pi, NL, E.C, F.data) ? HB_BF_LOAD16 : 0u) | ((uintptr_t)F.tags % 4 == 0 ? HB_BF_TAGS4 : 0u);
+            fill_rec<NL>(MC.primes.primes[MC.prime_of[(size_t)i]], pi, E.S, 0, slot0[(size_t)f], hrecs[f]);
+            // the conversion pass's view of the file: its slot range
+            hslots[f] = PbProof{slot0[(size_t)f], nullptr, 0, nullptr, 0, E.S, 0u};
+        }
+        if (doff != L.up_bytes || toff != L.total ||
+            hb_em_mac_wgs(Sv.data(), mbv.data(), nf, T, L.at<HbEmWg>(host, HB_EMX_WGS), &nsplit2) != nwg || nsplit2 != nsplit ||
+            hb_mixed_mont_wgs(Sv.data(), nf, L.at<HbMxWg>(host, HB_EMX_MONTWG)) != nmwg)
+            return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        if (cxx) memcpy(host + L.off[HB_EMX_JOBS], plan.jobs.data() + G.job0, (size_t)(nj * sizeof(HbCbJob)));
+        else if (hb_em_jobs(Sv.data(), nbv.data(), nf, L.at<HbEmJob>(host, HB_EMX_JOBS)) != nj)
+            return fail(c, HB_EHIP, "internal: batch tables do not add up");
+        unsigned long long qs[2 * HB_QSLOT];
+        auto launch = [&]() -> int {
+            const MxRec<NL> *recs = L.at<const MxRec<NL>>(dev, HB_EMX_RECS);
+            u32 *fv = L.at<u32>(dev, HB_EMX_FV), *am = L.at<u32>(dev, HB_EMX_AM);
+            if (cxx) {
+                CemPrfArgs<NL> A;
+                memset(&A, 0, sizeof A);
+                A.prf = L.at<const PrfParams<NL>>(dev, HB_EMX_PRF);
+                A.files = L.at<const BatchFile>(dev, HB_EMX_FILES);
+                A.jobs = L.at<const HbCbJob>(dev, HB_EMX_JOBS);
+                A.njobs = nj;
+                A.recs = recs;
+                A.fv = fv;
+                A.araw = am;
+                A.t0 = c->t0;
+                A.queue = c->queue;
+                HB_CHECK(hb_launch_cemixed_prf<NL>(A, nr, batch_grid(c, nj), c->stream), "hb_cemixed_prf_kernel launch");
+            } else {
+                EmPrfArgs<NL> A;
+                memset(&A, 0, sizeof A);
+                A.prf = L.at<const PrfParams<NL>>(dev, HB_EMX_PRF);
+                A.files = L.at<const BatchFile>(dev, HB_EMX_FILES);
+                A.jobs = L.at<const BatchWaveJob>(dev, HB_EMX_JOBS);
+                A.njobs = nj;
+                A.recs = recs;
+                A.fv = fv;
+                A.araw = am;
+                A.t0 = c->t0;
+                A.queue = c->queue;
+                HB_CHECK(hb_launch_emixed_prf<NL>(A, nr, batch_grid(c, (nj + 15) / 16), c->stream), "hb_emixed_prf_kernel launch");
+            }
+            MxMontArgs<NL> Tm;
+            memset(&Tm, 0, sizeof Tm);
+            Tm.recs = recs;
+            Tm.proofs = L.at<const PbProof>(dev, HB_EMX_SLOTS);
+            Tm.wgs = L.at<const MxWg>(dev, HB_EMX_MONTWG);
+            Tm.vv = am;
+            HB_CHECK(hb_launch_mixed_mont<NL>(Tm, (u32)nmwg, c->stream), "hb_mixed_mont_kernel launch");
+            c->last_launches += 2;
+            if (nwg) {
+                EmMacArgs<NL> M;
+                memset(&M, 0, sizeof M);
+                M.recs = recs;
+                M.files = L.at<const BatchFile>(dev, HB_EMX_FILES);
+                M.wgs = L.at<const BatchMacWg>(dev, HB_EMX_WGS);
+                M.fv = fv;
+                M.amont = am;
+                HB_CHECK(hb_launch_emixed_mac<NL>(M, (u32)nsplit, (u32)(nwg - nsplit), c->stream), "hb_emixed_mac kernels launch");
+                c->last_launches += (nsplit ? 1u : 0u) + (nwg > nsplit ? 1u : 0u);
+            }
+            return 0;
+        };
+        // slots 0 (wave-job counter, F tries) and 1 (alpha)
+        if (int rc = group_transport(c, L, 2, launch, HB_EMX_TAGS, tags_dev ? nullptr : "hipMemcpyAsync(D2H tags)", qs,
+                                     cxx ? "mixed batched cxx encode" : "mixed batched encode"))
+            return rc;
+        if (!cxx && (qs[2] || qs[HB_QSLOT + 2]))
+            return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate for some blocks");
+        tries += qs[1];
+        if (!tags_dev)
+            for (u64 f = 0, off = 0; f < nf; ++f)
+                off = stage_out(descs[cls[g[f]]].d.tags, host, off, nbv[(size_t)f] * MC.pi[(size_t)cls[g[f]]].tw);
+        return 0;
+    };
+
+    int rc = 0;
+    for (size_t k = 0; k < plan.groups.size() && !rc; ++k) rc = run_group(plan.groups[k]);
+    return batch_finish(c, rc, true, 2, plan.through, true, [&](u64 k) -> int {
+        const u64 i = cls[k];
+        const hb_encode_mixed_desc &X = descs[i];
+        u64 t = 0;
+        const int r = encode_impl<NL>(c, X.p_be, (size_t)X.p_len, MC.pi[(size_t)i], (u32)X.sectors, X.d.f_key, X.d.alpha_key,
+                                      key_len, 0, X.d.data, X.d.len, shape_of(i).blocks_of(X.d), X.d.tags,
+                                      (flags & (HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE)) | (cxx ? (u32)HB_PRF_CXX : 0u), &t);
+        if (r) return r;
+        tries += t;
+        c->last_ms = 0.0;   // (the call's, not the last single encode's)
+        c->ph_valid = false;
+        return 0;
+    });
+}
+
 }  // namespace
 
 // ================================================================== C ABI
@@ -4531,6 +4751,49 @@ int check_file_descs(hb_ctx *c, const hb_file_desc *files, u64 n, bool cxx) {
     return 0;
 }
 
+// hb_encode_mixed and hb_cxx_encode_mixed (cxx): every descriptor checked with
+// the single encode's rules for its own prime, the primes through the call's
+// cache, then class by class.
+int encode_mixed(hb_ctx *c, const hb_encode_mixed_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out, bool cxx) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (cxx && (flags & ~(uint32_t)(HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE)))
+        return fail(c, HB_EUNSUPPORTED, "hb_cxx_encode_mixed takes HB_DATA_ON_DEVICE and HB_TAGS_ON_DEVICE only");
+    if (!cxx && (flags & (uint32_t)(HB_PRF_CXX | HB_ASYNC | HB_ENCODE_SINGLE_PASS)))
+        return fail(c, HB_EUNSUPPORTED, "hb_encode_mixed takes no HB_PRF_CXX, HB_ASYNC or HB_ENCODE_SINGLE_PASS");
+    if (tries_out) *tries_out = 0;
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "files is NULL");
+    MixedCall MC;
+    MC.pi.resize((size_t)nfiles);
+    MC.prime_of.resize((size_t)nfiles);
+    std::vector<uint32_t> nl((size_t)nfiles), nr((size_t)nfiles);
+    for (u64 i = 0; i < nfiles; ++i) {
+        const hb_encode_mixed_desc &X = files[i];
+        const std::string who = "file " + std::to_string(i) + ": ";
+        PrimeInfo &pi = MC.pi[(size_t)i];
+        if (int rc = check_mixed_head(c, who, X.p_be, X.p_len, X.key_len, X.key_len, X.sectors, pi)) return rc;
+        if (!X.d.f_key || !X.d.alpha_key) return fail(c, HB_EINVAL, who + "a key is NULL");
+        if (!X.d.tags) return fail(c, HB_EINVAL, who + "tags buffer is NULL");
+        if (!X.d.data && X.d.len) return fail(c, HB_EINVAL, who + "data buffer is NULL");
+        if (cxx && (pi.tw % 16 != 0 || pi.tw > 4u * (u32)pi.nl))
+            return fail(c, HB_EUNSUPPORTED, who + "cxx prf mode needs ByteCount(p) to be a multiple of 16");
+        nl[(size_t)i] = (uint32_t)pi.nl;
+        nr[(size_t)i] = hb_mx_rounds(X.key_len);
+    }
+    for (u64 i = 0; i < nfiles; ++i) MC.prime_of[(size_t)i] = MC.primes.get(files[i].p_be, (size_t)files[i].p_len, nl[(size_t)i]);
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    u64 tries = 0;
+    const int rc = mixed_classes(c, nl, nr, [&](const HbMxClass &K) {
+        return by_nl(c, (int)K.nl, [&](auto NL) {
+            return encode_mixed_impl<HB_NL(NL)>(c, files, K.items, (int)K.nr, flags, cxx, MC, tries);
+        });
+    });
+    if (rc) return rc;
+    if (tries_out) *tries_out = tries;
+    return 0;
+}
+
 int verify_rhs(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors,
                const uint8_t *f_key, const uint8_t *alpha_key, size_t key_len,
                uint64_t state_chunks, const uint8_t *chal_key, size_t chal_key_len, uint64_t chunks,
@@ -4608,6 +4871,14 @@ int hb_cxx_encode_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t se
     return by_nl(c, pi.nl, [&](auto NL) {
         return cxx_encode_many_impl<HB_NL(NL)>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
     });
+}
+
+int hb_encode_mixed(hb_ctx *c, const hb_encode_mixed_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {
+    return encode_mixed(c, files, nfiles, flags, tries_out, false);
+}
+
+int hb_cxx_encode_mixed(hb_ctx *c, const hb_encode_mixed_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {
+    return encode_mixed(c, files, nfiles, flags, tries_out, true);
 }
 
 int hb_prove_range(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors,

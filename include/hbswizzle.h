@@ -626,6 +626,73 @@ int hb_cxx_prove_mixed(hb_ctx *ctx, const hb_prove_mixed_desc *proofs, uint64_t 
  * written. */
 int hb_cxx_verify_rhs_mixed(hb_ctx *ctx, const hb_verify_mixed_desc *proofs, uint64_t nproofs, uint32_t flags);
 
+/* hb_encode_many for the files of many owners: every file names its own
+ * prime, `sectors` and key length.  A PySwizzle instance draws its own prime
+ * (heartbeat/PySwizzle/PySwizzle.py:250-251), so a process that keeps one beat
+ * per owner, contract or farmer and tags one file for each has one prime per
+ * file, not one per batch.  Replaces that process's loop of hb_encode
+ * (PySwizzle.py:279-311 per file): file i's tag buffer
+ * (hb_block_count(its own p, its own sectors, len) * hb_width(its own p)
+ * bytes) receives exactly the bytes hb_encode writes for the same prime,
+ * sectors, keys and data with block_base = 0 and nblocks = hb_block_count(...),
+ * PySwizzle's KeyedPRF.  The files are split into classes by the prime's limb
+ * count (256 / 512 / 1024 / 2048 bits) and the key's AES round count; a class
+ * is grouped under hb_encode_many's caps and a group is one H2D copy, three
+ * launches -- the PRF launch (F of every block, alpha of every sector, each
+ * file's schedules with its own range), a conversion pass alpha -> alpha R
+ * mod p over the group's alpha slots under each file's modulus, and one MAC
+ * launch whose workgroups each take blocks of one file and read that file's
+ * modulus, block size, sector size, sector count, tag width and first alpha
+ * slot from a per-file device record -- and one D2H copy.  The Montgomery
+ * constants are computed once per distinct prime of the call.  A file with
+ * more blocks than hb_encode_many batches, or which alone exceeds the group's
+ * scratch cap, goes through the single encode under its own prime and
+ * `sectors` inside the same call.
+ * flags applies to the whole call and means what it means in hb_encode_many:
+ * HB_DATA_ON_DEVICE / HB_TAGS_ON_DEVICE (device pointers of any alignment);
+ * HB_HOST_REGISTER is ignored; HB_PRF_CXX, HB_ASYNC and HB_ENCODE_SINGLE_PASS
+ * return HB_EUNSUPPORTED.  nfiles == 0 returns HB_OK.  Every descriptor is
+ * checked before any GPU work with hb_encode's rules and codes for that
+ * file's own arguments (a prime above 2048 bits or below 2^8, an even prime,
+ * sectors == 0 or not below 2^32, a key length other than 16 / 24 / 32, a NULL
+ * key or tag buffer, a NULL data buffer with len > 0); hb_last_error names the
+ * file ("file 3: ...") and no tag buffer is written.  *tries_out (may be
+ * NULL) receives the sum of the files' F tries: what nfiles hb_encode calls
+ * report in total. */
+typedef struct hb_encode_mixed_desc {  /* nine 8-byte words, in this order */
+    const uint8_t *p_be;               /* this file's prime, big-endian */
+    uint64_t p_len;
+    uint64_t sectors;                  /* this file's S (below 2^32) */
+    uint64_t key_len;                  /* f_key / alpha_key bytes: 16, 24 or 32 */
+    hb_file_desc d;                    /* the five words of hb_file_desc, same meaning */
+} hb_encode_mixed_desc;
+
+int hb_encode_mixed(hb_ctx *ctx, const hb_encode_mixed_desc *files, uint64_t nfiles,
+                    uint32_t flags, uint64_t *tries_out);
+
+/* hb_cxx_encode_many for the files of many owners: every cxx Swizzle draws
+ * its own prime (init, cxx/shacham_waters_private.cxx:596-624).  Replaces a
+ * loop over cxx/shacham_waters_private.cxx:638-702 with the prf of
+ * cxx/prf.hxx:125-176 (one hb_encode with HB_PRF_CXX per file): file i's tags
+ * are exactly the bytes hb_encode(..., HB_PRF_CXX) writes for that file's own
+ * prime, sectors, keys and data with block_base = 0 and nblocks =
+ * hb_block_count(...); a block that reads no sector under the file's OWN
+ * block size (the last one of a file whose length is a multiple of it; the
+ * only one of an empty file) keeps F as the prf returned it (:681-690).
+ * Takes hb_encode_mixed_desc unchanged.  Classes, groups and fall-through as
+ * in hb_encode_mixed; a group is one H2D copy, the PRF launch (one lane per
+ * evaluation, wave-jobs of up to 64 evaluations of one file under one key,
+ * longest first), the conversion pass, the MAC launch of hb_encode_mixed
+ * (none when no block of the group reads a sector) and one D2H copy.
+ * flags: HB_DATA_ON_DEVICE and/or HB_TAGS_ON_DEVICE; anything else returns
+ * HB_EUNSUPPORTED.  nfiles == 0 returns HB_OK.  Every descriptor is checked
+ * before any GPU work with hb_encode(HB_PRF_CXX)'s rules and codes for that
+ * file's own arguments -- a prime whose ByteCount is not a multiple of 16
+ * fails the call with HB_EUNSUPPORTED -- hb_last_error names the file and no
+ * tag buffer is written.  Parity unpinned, as every cxx entry point. */
+int hb_cxx_encode_mixed(hb_ctx *ctx, const hb_encode_mixed_desc *files, uint64_t nfiles,
+                        uint32_t flags, uint64_t *tries_out);
+
 /* Host AES-CFB8 (segment 8, any 16-byte IV) for PySwizzle State
  * encrypt/decrypt (PySwizzle.py:162-195): 64 bytes per call, not a hot path.
  * encrypt = 1 encrypts, 0 decrypts. */
