@@ -31,9 +31,10 @@ import numpy as np
 from .. import _many, _native, multi
 from .._filebuf import FileBuffer
 from ..exc import HeartbeatError
+from ..primes import getPrimes
 from ..util import KeyedPRF, hb_decode, hb_encode
 
-__all__ = ["KeyedPRF", "Challenge", "Tag", "State", "Proof", "PySwizzle", "getPrime"]
+__all__ = ["KeyedPRF", "Challenge", "Tag", "State", "Proof", "PySwizzle", "getPrime", "getPrimes"]
 
 AES_BLOCK = 16
 
@@ -257,6 +258,13 @@ class PySwizzle(object):
         self.prime = getPrime(primebits) if prime is None else prime
         self.sectors = sectors
         self.sectorsize = self.prime.bit_length() // 8
+
+    @staticmethod
+    def generate_many(count, sectors=10, primebits=1024):
+        """`count` new objects, each with its own random key and its own
+        prime: the primes are drawn together on the GPU (primes.getPrimes)
+        instead of one getPrime per constructor."""
+        return [PySwizzle(sectors, None, p, primebits) for p in getPrimes(primebits, count)]
 
     def todict(self):
         return {"key": hb_encode(self.key), "prime": self.prime, "sectors": self.sectors}

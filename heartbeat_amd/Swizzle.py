@@ -40,6 +40,7 @@ from . import _many, _native, multi
 from ._filebuf import FileBuffer
 from .exc import HeartbeatError
 from .PySwizzle.PySwizzle import _kb, _random_bytes, getPrime
+from .primes import getPrimes
 
 __all__ = ["Swizzle", "Tag", "State", "Challenge", "Proof"]
 
@@ -369,6 +370,13 @@ class Swizzle(_Serializable):
             if prime is None:
                 self.prime = getPrime(PRIME_BITS)
         self.sectorsize = self.prime.bit_length() // 8   # _p.BitCount()/8 (:621)
+
+    @classmethod
+    def generate_many(cls, count, check_fraction=1.0, sectors=10):
+        """`count` new objects, each with its own random keys and its own
+        prime: the primes are drawn together on the GPU (primes.getPrimes)
+        instead of one getPrime per constructor."""
+        return [cls(check_fraction, sectors, True, p) for p in getPrimes(PRIME_BITS, count)]
 
     # -- serialisation (:844-976)
     def __reduce__(self):

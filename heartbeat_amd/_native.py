@@ -105,6 +105,9 @@ SIGNATURES = [
                                    _c.POINTER(_c.c_uint64)]),
     ("hb_cxx_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,
                                        _c.POINTER(_c.c_uint64)]),
+    ("hb_mr_test", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint64, _B, _c.c_uint32, _P]),
+    ("hb_prime_search", _c.c_int, [_P, _c.c_uint32, _B, _c.c_uint64, _c.c_uint32, _B, _c.c_uint32, _P, _P,
+                                   _c.POINTER(_c.c_uint64)]),
     ("hb_block_count", _c.c_uint64, [_B, _c.c_size_t, _c.c_uint32, _c.c_uint64]),
     ("hb_prove", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _c.c_size_t, _c.c_uint64, _B,
                             _c.c_size_t, _P, _c.c_uint64, _P, _c.c_uint64, _c.c_uint32, _P, _P]),

@@ -34,10 +34,12 @@
 #include "hb_mixed_args.hpp"
 #include "hb_cmixed_args.hpp"
 #include "hb_emixed_args.hpp"
+#include "hb_prime_args.hpp"
 #include "hb_bignum_host.hpp"
 #include "hb_batch_host.hpp"
 #include "hb_mixed_host.hpp"
 #include "hb_emixed_host.hpp"
+#include "hb_prime_host.hpp"
 
 using namespace hbhost;
 
@@ -85,6 +87,9 @@ template <int NL> hipError_t hb_launch_emixed_prf(const EmPrfArgs<NL> &, int, in
 template <int NL> hipError_t hb_launch_cemixed_prf(const CemPrfArgs<NL> &, int, int, hipStream_t);
 template <int NL> u32 hb_emixed_mac_threads();
 template <int NL> hipError_t hb_launch_emixed_mac(const EmMacArgs<NL> &, u32, u32, hipStream_t);
+// hb_prime.hpp (hb_kern_prime*.hip)
+template <int NL> hipError_t hb_launch_prime_test(const PrTestArgs &, bool, hipStream_t);
+template <int NL> hipError_t hb_launch_prime_sieve(const PrSieveArgs &, u32, u32, hipStream_t);
 
 namespace {
 
@@ -167,6 +172,10 @@ struct hb_ctx {
     HostBuf gstage[2];   // host-file prove: pinned gather buffers (blocks | tags), double-buffered
     DevBuf bdev;         // hb_encode_many: tables | host files | F | alpha | tags of one group of files
     HostBuf bhost;       // its pinned staging: tables | host files, and the tags coming back
+    // hb_mr_test / hb_prime_search: numbers, bases, jobs, verdicts; the sieve's
+    // primes (written once: pr_q_n), windows, survivors and counts
+    DevBuf pr_src, pr_bases, pr_jobs, pr_pass, pr_q, pr_win, pr_surv, pr_cnt;
+    u32 pr_q_n = 0;
     HostBuf hscratch;    // pinned staging of the encode's small host round trips (alpha, MFMA tables)
     // the alpha D2H into hscratch done / the MFMA-table H2D out of it done
     // (not yet waited for: the next round trip must wait before reusing hscratch)
@@ -4339,7 +4348,8 @@ void hb_ctx_destroy(hb_ctx *c) {
     DevBuf *bufs[] = {&c->alpha_raw, &c->alpha_mont, &c->xs, &c->vals, &c->vals2, &c->wts, &c->idx,
                       &c->partials, &c->sums, &c->data[0], &c->data[1], &c->tags, &c->blen, &c->gtags,
                       &c->pfx, &c->retry, &c->ctl, &c->afrag, &c->mseeds, &c->moffs, &c->mdig, &c->gdev,
-                      &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig, &c->bdev};
+                      &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig, &c->bdev, &c->pr_src, &c->pr_bases,
+                      &c->pr_jobs, &c->pr_pass, &c->pr_q, &c->pr_win, &c->pr_surv, &c->pr_cnt};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
@@ -4812,9 +4822,264 @@ int verify_rhs(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors,
     });
 }
 
+// ------------------------------------------------------------------ primes
+// hb_mr_test and hb_prime_search (hb_prime.hpp): a lane per (candidate, base).
+// The 64-bit class (NL = 2) exists for these two entries only.
+template <class F>
+int by_prime_nl(hb_ctx *c, int nl, F &&f) {
+    if (nl == 2) return f(std::integral_constant<int, 2>());
+    return by_nl(c, nl, f);
+}
+
+// jobs of one launch at the most: bounds the grid and the job table
+const size_t kPrimeLaunchJobs = (size_t)1 << 22;
+// lanes that fill the machine once: a wave per SIMD
+u64 prime_capacity(const hb_ctx *c) { return (u64)c->num_cus * 4u * HB_PR_TEST_WG; }
+
+void be_to_limbs(const uint8_t *be, size_t n, u32 *out, size_t nl) {
+    for (size_t t = 0; t < nl; ++t) out[t] = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t pos = n - 1 - k;
+        out[pos / 4] |= (u32)be[k] << (8 * (pos % 4));
+    }
+}
+
+// value of the big-endian string if it is below 2^32, else 0xffffffff
+u32 be_small(const uint8_t *be, size_t n) {
+    u64 v = 0;
+    for (size_t k = 0; k < n; ++k) {
+        v = (v << 8) | be[k];
+        if (v > 0xffffffffull) return 0xffffffffu;
+    }
+    return (u32)v;
+}
+
+// The verdicts of `jobs` over the numbers and bases already in c->pr_src /
+// c->pr_bases, in launches of kPrimeLaunchJobs jobs at the most.
+template <int NL>
+int prime_launch(hb_ctx *c, const std::vector<PrJob> &jobs, bool base2, u32 maxbits, std::vector<u32> &pass) {
+    pass.resize(jobs.size());
+    for (size_t off = 0; off < jobs.size(); off += kPrimeLaunchJobs) {
+        const size_t n = jobs.size() - off < kPrimeLaunchJobs ? jobs.size() - off : kPrimeLaunchJobs;
+        HB_CHECK(c->pr_jobs.ensure(n * sizeof(PrJob)), "hipMalloc");
+        HB_CHECK(c->pr_pass.ensure(n * 4), "hipMalloc");
+        HB_CHECK(hipMemcpyAsync(c->pr_jobs.p, jobs.data() + off, n * sizeof(PrJob), hipMemcpyHostToDevice, c->stream),
+                 "H2D(jobs)");
+        PrTestArgs A;
+        A.src = (const u32 *)c->pr_src.p;
+        A.bases = base2 ? nullptr : (const u32 *)c->pr_bases.p;
+        A.jobs = (const PrJob *)c->pr_jobs.p;
+        A.pass = (u32 *)c->pr_pass.p;
+        A.njobs = n;
+        A.maxbits = maxbits;
+        HB_CHECK(hb_launch_prime_test<NL>(A, base2, c->stream), "hb_prime_test_kernel launch");
+        ++c->last_launches;
+        HB_CHECK(hipMemcpyAsync(pass.data() + off, c->pr_pass.p, n * 4, hipMemcpyDeviceToHost, c->stream), "D2H(pass)");
+        HB_CHECK(hipStreamSynchronize(c->stream), "hb_prime_test_kernel");
+    }
+    return 0;
+}
+
+template <int NL>
+int mr_test_impl(hb_ctx *c, const uint8_t *cands_be, size_t width, u64 ncands, const uint8_t *bases_be, u32 rounds,
+                 u32 maxbits, uint8_t *verdicts) {
+    // candidates per pass: about 2^20 jobs, so that the buffers stay small
+    const u64 per = ((u64)1 << 20) / rounds ? ((u64)1 << 20) / rounds : 1;
+    std::vector<u32> src, bases, pass;
+    std::vector<PrJob> jobs;
+    std::vector<uint8_t> out(ncands);
+    for (u64 c0 = 0; c0 < ncands; c0 += per) {
+        const u64 nc = ncands - c0 < per ? ncands - c0 : per;
+        src.resize(nc * NL);
+        bases.resize(nc * rounds * NL);
+        jobs.resize(nc * rounds);
+        for (u64 i = 0; i < nc; ++i) {
+            be_to_limbs(cands_be + (c0 + i) * width, width, &src[i * NL], NL);
+            for (u32 r = 0; r < rounds; ++r) {
+                const u64 b = i * rounds + r;
+                be_to_limbs(bases_be + ((c0 + i) * rounds + r) * width, width, &bases[b * NL], NL);
+                jobs[b] = PrJob{(u32)i, 0u, (u32)b};
+            }
+        }
+        HB_CHECK(c->pr_src.ensure(src.size() * 4), "hipMalloc");
+        HB_CHECK(c->pr_bases.ensure(bases.size() * 4), "hipMalloc");
+        HB_CHECK(hipMemcpyAsync(c->pr_src.p, src.data(), src.size() * 4, hipMemcpyHostToDevice, c->stream), "H2D(candidates)");
+        HB_CHECK(hipMemcpyAsync(c->pr_bases.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice, c->stream), "H2D(bases)");
+        if (int rc = prime_launch<NL>(c, jobs, false, maxbits, pass)) return rc;
+        for (u64 i = 0; i < nc; ++i) {
+            uint8_t all = 1;
+            for (u32 r = 0; r < rounds; ++r) all &= pass[i * rounds + r] ? 1 : 0;
+            out[c0 + i] = all;
+        }
+    }
+    memcpy(verdicts, out.data(), ncands);   // nothing is written unless every pass completed
+    return 0;
+}
+
+template <int NL>
+int prime_search_impl(hb_ctx *c, u32 bits, size_t width, const uint8_t *starts_be, u64 nstarts, u32 window,
+                      const uint8_t *bases_be, u32 rounds, uint8_t *primes_be, uint8_t *found, u64 &tests) {
+    if (c->pr_q_n == 0) {   // the sieve's primes, once per context
+        const std::vector<u32> q = ps_sieve_primes();
+        HB_CHECK(c->pr_q.ensure(q.size() * 4), "hipMalloc");
+        HB_CHECK(hipMemcpy(c->pr_q.p, q.data(), q.size() * 4, hipMemcpyHostToDevice), "H2D(sieve primes)");
+        c->pr_q_n = (u32)q.size();
+    }
+    // starts per pass: survivor lists of 32 MiB at the most
+    const u64 per = ((u64)16 << 20) / window ? ((u64)16 << 20) / window : 1;
+    const u64 capacity = prime_capacity(c);
+    std::vector<u32> src, bases, win, count, pass;
+    std::vector<uint16_t> surv;
+    std::vector<PrJob> jobs;
+    for (u64 s0 = 0; s0 < nstarts; s0 += per) {
+        const u64 ns = nstarts - s0 < per ? nstarts - s0 : per;
+        src.resize(ns * NL);
+        win.resize(ns);
+        bases.resize(ns * rounds * NL);
+        for (u64 i = 0; i < ns; ++i) {
+            be_to_limbs(starts_be + (s0 + i) * width, width, &src[i * NL], NL);
+            win[i] = ps_window_limit(Limbs(src.begin() + i * NL, src.begin() + (i + 1) * NL), bits, window);
+            for (u32 r = 0; r < rounds; ++r)
+                be_to_limbs(bases_be + ((s0 + i) * rounds + r) * width, width, &bases[(i * rounds + r) * NL], NL);
+        }
+        HB_CHECK(c->pr_src.ensure(src.size() * 4), "hipMalloc");
+        HB_CHECK(c->pr_bases.ensure(bases.size() * 4), "hipMalloc");
+        HB_CHECK(c->pr_win.ensure(ns * 4), "hipMalloc");
+        HB_CHECK(c->pr_cnt.ensure(ns * 4), "hipMalloc");
+        HB_CHECK(c->pr_surv.ensure(ns * window * 2), "hipMalloc");
+        HB_CHECK(hipMemcpyAsync(c->pr_src.p, src.data(), src.size() * 4, hipMemcpyHostToDevice, c->stream), "H2D(starts)");
+        if (!bases.empty())
+            HB_CHECK(hipMemcpyAsync(c->pr_bases.p, bases.data(), bases.size() * 4, hipMemcpyHostToDevice, c->stream), "H2D(bases)");
+        HB_CHECK(hipMemcpyAsync(c->pr_win.p, win.data(), ns * 4, hipMemcpyHostToDevice, c->stream), "H2D(windows)");
+        PrSieveArgs SA;
+        SA.starts = (const u32 *)c->pr_src.p;
+        SA.win = (const u32 *)c->pr_win.p;
+        SA.q = (const u32 *)c->pr_q.p;
+        SA.nq = c->pr_q_n;
+        SA.stride = window;
+        SA.surv = (unsigned short *)c->pr_surv.p;
+        SA.count = (u32 *)c->pr_cnt.p;
+        HB_CHECK(hb_launch_prime_sieve<NL>(SA, (u32)ns, window, c->stream), "hb_prime_sieve_kernel launch");
+        ++c->last_launches;
+        count.resize(ns);
+        surv.resize(ns * window);
+        HB_CHECK(hipMemcpyAsync(count.data(), c->pr_cnt.p, ns * 4, hipMemcpyDeviceToHost, c->stream), "D2H(counts)");
+        HB_CHECK(hipMemcpyAsync(surv.data(), c->pr_surv.p, surv.size() * 2, hipMemcpyDeviceToHost, c->stream), "D2H(survivors)");
+        HB_CHECK(hipStreamSynchronize(c->stream), "hb_prime_sieve_kernel");
+        std::vector<PsStart> S(ns);
+        for (u64 i = 0; i < ns; ++i) {
+            if (count[i] > win[i]) return fail(c, HB_EHIP, "the sieve reported more survivors than candidates");
+            S[i].surv = &surv[i * window];
+            S[i].count = count[i];
+        }
+        while (ps_plan_base2(S, capacity, jobs)) {
+            tests += jobs.size();
+            if (int rc = prime_launch<NL>(c, jobs, true, bits, pass)) return rc;
+            ps_select(S, pass.data());
+            ps_plan_full(S, rounds, jobs);
+            tests += jobs.size();
+            if (int rc = prime_launch<NL>(c, jobs, false, bits, pass)) return rc;
+            ps_apply_full(S, rounds, pass.data());
+        }
+        for (u64 i = 0; i < ns; ++i) {
+            uint8_t *out = primes_be + (s0 + i) * width;
+            memset(out, 0, width);
+            found[s0 + i] = S[i].found != PS_NONE;
+            if (S[i].found == PS_NONE) continue;
+            u32 n[NL];
+            u64 cy = 2ull * S[i].surv[S[i].found];
+            for (int t = 0; t < NL; ++t) {
+                cy += src[i * NL + t];
+                n[t] = (u32)cy;
+                cy >>= 32;
+            }
+            to_be(n, NL, out, width);
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hb_mr_test(hb_ctx *c, const uint8_t *cands_be, size_t width, uint64_t ncands, const uint8_t *bases_be,
+               uint32_t rounds, uint8_t *verdicts) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (width == 0) return fail(c, HB_EINVAL, "width must be at least 1 byte");
+    if (width > 256) return fail(c, HB_EUNSUPPORTED, "candidates above 256 bytes are not supported");
+    const int nl = nl_for_bits(8 * (int)width);
+    if (!nl) return fail(c, HB_EUNSUPPORTED, "candidates above 1024 bits are not supported by this build");
+    if (rounds == 0) return fail(c, HB_EINVAL, "rounds must be at least 1");
+    if (rounds > 65536) return fail(c, HB_EUNSUPPORTED, "more than 65536 rounds are not supported");
+    if (ncands == 0) return 0;
+    if (!cands_be || !bases_be || !verdicts) return fail(c, HB_EINVAL, "candidates, bases or verdicts buffer is NULL");
+    u32 maxbits = 0;
+    std::vector<uint8_t> nm2(width);
+    for (u64 i = 0; i < ncands; ++i) {
+        const uint8_t *n = cands_be + i * width;
+        const std::string who = "candidate " + std::to_string(i);
+        if (!(n[width - 1] & 1)) return fail(c, HB_EINVAL, who + " is even");
+        if (be_small(n, width) < 5) return fail(c, HB_EINVAL, who + " is below 5");
+        const u32 bl = (u32)bitlen_be(n, width);
+        if (bl > maxbits) maxbits = bl;
+        // n - 2 (n odd and >= 5: the borrow ends)
+        memcpy(nm2.data(), n, width);
+        for (size_t k = width, sub = 2; k-- > 0 && sub;) {
+            const int d = (int)nm2[k] - (int)sub;
+            nm2[k] = (uint8_t)(d & 0xff);
+            sub = d < 0 ? 1 : 0;
+        }
+        for (u32 r = 0; r < rounds; ++r) {
+            const uint8_t *a = bases_be + (i * rounds + r) * width;
+            if (be_small(a, width) < 2 || memcmp(a, nm2.data(), width) > 0)
+                return fail(c, HB_EINVAL, who + ": base " + std::to_string(r) + " is outside [2, n - 2]");
+        }
+    }
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    c->last_launches = 0;
+    return by_prime_nl(c, nl, [&](auto NL) {
+        return mr_test_impl<HB_NL(NL)>(c, cands_be, width, ncands, bases_be, rounds, maxbits, verdicts);
+    });
+}
+
+int hb_prime_search(hb_ctx *c, uint32_t bits, const uint8_t *starts_be, uint64_t nstarts, uint32_t window,
+                    const uint8_t *bases_be, uint32_t rounds, uint8_t *primes_be, uint8_t *found,
+                    uint64_t *tests_out) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (tests_out) *tests_out = 0;
+    if (bits < 8 || bits > 2048) return fail(c, HB_EINVAL, "bits must be in [8, 2048]");
+    if (window < 1 || window > HB_PR_MAX_WINDOW) return fail(c, HB_EINVAL, "window must be in [1, 65536]");
+    if (rounds > 65536) return fail(c, HB_EUNSUPPORTED, "more than 65536 rounds are not supported");
+    const int nl = nl_for_bits((int)bits);
+    if (!nl) return fail(c, HB_EUNSUPPORTED, "primes above 1024 bits are not supported by this build");
+    if (nstarts == 0) return 0;
+    if (!starts_be || !primes_be || !found || (rounds && !bases_be))
+        return fail(c, HB_EINVAL, "starts, bases, primes or found buffer is NULL");
+    const size_t width = (bits + 7) / 8;
+    for (u64 i = 0; i < nstarts; ++i) {
+        const uint8_t *n = starts_be + i * width;
+        const std::string who = "start " + std::to_string(i);
+        if (!(n[width - 1] & 1)) return fail(c, HB_EINVAL, who + " is even");
+        if ((u32)bitlen_be(n, width) != bits) return fail(c, HB_EINVAL, who + " does not have exactly `bits` bits");
+        for (u32 r = 0; r < rounds; ++r) {
+            const uint8_t *a = bases_be + (i * rounds + r) * width;
+            if (be_small(a, width) < 2 || (u32)bitlen_be(a, width) > bits - 1)
+                return fail(c, HB_EINVAL, who + ": base " + std::to_string(r) + " is outside [2, 2^(bits-1) - 1]");
+        }
+    }
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    c->last_launches = 0;
+    u64 tests = 0;
+    const int rc = by_prime_nl(c, nl, [&](auto NL) {
+        return prime_search_impl<HB_NL(NL)>(c, bits, width, starts_be, nstarts, window, bases_be, rounds, primes_be,
+                                            found, tests);
+    });
+    if (tests_out) *tests_out = tests;
+    return rc;
+}
 
 int hb_encode(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors,
               const uint8_t *f_key, const uint8_t *alpha_key, size_t key_len,

@@ -693,7 +693,51 @@ int hb_encode_mixed(hb_ctx *ctx, const hb_encode_mixed_desc *files, uint64_t nfi
 int hb_cxx_encode_mixed(hb_ctx *ctx, const hb_encode_mixed_desc *files, uint64_t nfiles,
                         uint32_t flags, uint64_t *tries_out);
 
-/* Host AES-CFB8 (segment 8, any 16-byte IV) for PySwizzle State
+/* Strong-probable-prime tests, a lane per (candidate, base).  Replaces the
+ * Miller-Rabin rounds of getPrime (PySwizzle.py:74-77): many candidates and
+ * many bases in one launch, each lane deriving its own Montgomery constants
+ * (csrc/hb_prime.hpp).  Deterministic: the bases come from the caller.
+ *
+ * cands_be: ncands numbers of `width` bytes each (1..256, big-endian, leading
+ * zero bytes allowed), every one odd and >= 5; the limb class is the smallest
+ * that holds `width`.  bases_be: ncands x rounds x width bytes, base r of
+ * candidate i at (i * rounds + r) * width, each in [2, n_i - 2]; 1 <= rounds
+ * <= 65536.  verdicts[i] = 1 iff candidate i is a strong probable prime to
+ * EACH of its bases, else 0.  That is the exact function, not "is prime":
+ * 3215031751 = 151 * 751 * 28351 with bases 2, 3, 5, 7 gives 1.
+ * ncands == 0: HB_OK.  A bad argument (an even candidate, one below 5, a base
+ * outside [2, n - 2], rounds == 0): HB_EINVAL, hb_last_error names the
+ * candidate, and no verdict is written.  width > 256 (or > 128 in a build
+ * without the 2048-bit kernels), rounds > 65536: HB_EUNSUPPORTED.
+ * hb_last_kernel_ms's launch count covers this call. */
+int hb_mr_test(hb_ctx *ctx, const uint8_t *cands_be, size_t width, uint64_t ncands,
+               const uint8_t *bases_be, uint32_t rounds, uint8_t *verdicts);
+
+/* Incremental prime search from many starts at once.  Replaces a loop of
+ * getPrime (PySwizzle.py:74-77, one prime per owner object, :250-251).
+ *
+ * 8 <= bits <= 2048, width = ceil(bits / 8), 1 <= window <= 65536, rounds <=
+ * 65536 (0: base 2 alone; bases_be may then be NULL).  starts_be: nstarts x
+ * width bytes, each start odd with exactly `bits` bits.  bases_be: nstarts x
+ * rounds x width bytes, each base in [2, 2^(bits-1) - 1], which is inside
+ * [2, n - 2] for every candidate of that size.
+ * The result for start i is the SMALLEST n = start_i + 2k, 0 <= k < window,
+ * n < 2^bits, that is a strong probable prime to base 2 and to every
+ * bases_i[r]: found[i] = 1 and n in primes_be[i * width ..], big-endian; if
+ * there is none, found[i] = 0 and that slot is zero bytes.  How it gets there
+ * does not change that definition: a sieve by the odd primes below 2^16 per
+ * start (a candidate that is itself such a prime survives), base 2 tests over
+ * batches of survivors in ascending order, then a lane per base for the
+ * earliest survivor that passed; no candidate is reported unless every
+ * smaller survivor was tested and failed (csrc/hb_prime_host.hpp).
+ * *tests_out (may be NULL): the number of lane tests run.  nstarts == 0:
+ * HB_OK.  A bad argument: HB_EINVAL, hb_last_error names the start, nothing
+ * is written. */
+int hb_prime_search(hb_ctx *ctx, uint32_t bits, const uint8_t *starts_be, uint64_t nstarts,
+                    uint32_t window, const uint8_t *bases_be, uint32_t rounds,
+                    uint8_t *primes_be, uint8_t *found, uint64_t *tests_out);
+
+/* Host AES-CFB8(segment 8, any 16-byte IV) for PySwizzle State
  * encrypt/decrypt (PySwizzle.py:162-195): 64 bytes per call, not a hot path.
  * encrypt = 1 encrypts, 0 decrypts. */
 int hb_aes_cfb8(const uint8_t *key, size_t key_len, const uint8_t *iv,
