@@ -13,17 +13,26 @@ expect them.
 
 256-bit prime, S = 3, 16-byte keys, three items per call: files of 0, 95 and
 200 bytes (one block; a block boundary - 1; a short last sector), challenges
-of 1, 2 and >= state_chunks chunks (check_all on the cxx side)."""
+of 1, 2 and >= state_chunks chunks (check_all on the cxx side).
+
+A second test interleaves the one-prime prove and verify calls with their
+many-owner twins (hb_prove_mixed, hb_verify_rhs_mixed, hb_cxx_*_mixed) the same
+way: they share the code that fills a group's tables (hb_pv_host.hpp)."""
 import numpy as np
 import pytest
 
 import test_gpu_cxx_many as ce
 import test_gpu_cxx_prove_many as cp
+import test_gpu_cxx_prove_mixed as cpm
 import test_gpu_cxx_verify_many as cv
+import test_gpu_cxx_verify_mixed as cvm
 import test_gpu_encode_many as en
 import test_gpu_prove_many as pr
+import test_gpu_prove_mixed as pm
 import test_gpu_verify_many as ve
+import test_gpu_verify_mixed as vm
 from test_gpu_parity import P256
+from test_gpu_prove_many import P255
 
 pytestmark = pytest.mark.gpu
 
@@ -43,8 +52,10 @@ def nat():
 class Inputs(object):
     """The three items of every call, and what the single calls give for them."""
 
-    def __init__(self, nat):
-        rng = np.random.default_rng(20260)
+    def __init__(self, nat, p=P, S=S, seed=20260):
+        self.p, self.S = p, S
+        P = p
+        rng = np.random.default_rng(seed)
         w = nat.width_of(P)
         key = lambda: rng.integers(0, 256, KLEN, dtype=np.uint8).tobytes()   # noqa: E731
         self.datas = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in LENS]
@@ -57,6 +68,7 @@ class Inputs(object):
 
     def items(self, call, n):
         """Arguments of `call` for n items: the three, over and over."""
+        P = self.p
         k = [i % 3 for i in range(n)]
         if call in ("encode", "cxx_encode"):
             return [self.keys[i] for i in k], [self.datas[i] for i in k]
@@ -70,7 +82,7 @@ class Inputs(object):
 
     def singles(self, nat):
         """Every item through the single calls (on whatever nat.context() is)."""
-        W = self.want
+        W, P, S = self.want, self.p, self.S
         W["encode"] = [en.encode_single(nat, P, S, fk, ak, d)[0] for (fk, ak), d in zip(self.keys, self.datas)]
         W["cxx_encode"] = []
         for (fk, ak), d in zip(self.keys, self.datas):
@@ -86,11 +98,8 @@ class Inputs(object):
                 W[call].append(got)
 
 
-@pytest.fixture(scope="module")
-def inputs(nat, oracle):
-    """The inputs, the single calls' results from a fresh context, and the
-    oracle's for the single calls that follow every batched one."""
-    I = Inputs(nat)
+def fresh_singles(nat, I):
+    """I with the single calls' results from a fresh context."""
     shared = nat._ctxs
     nat._ctxs = {}
     try:
@@ -99,6 +108,14 @@ def inputs(nat, oracle):
         fresh, nat._ctxs = nat._ctxs, shared
         for c in fresh.values():
             c.close()
+    return I
+
+
+@pytest.fixture(scope="module")
+def inputs(nat, oracle):
+    """The inputs, the single calls' results from a fresh context, and the
+    oracle's for the single calls that follow every batched one."""
+    I = fresh_singles(nat, Inputs(nat))
     w = nat.width_of(P)
     fk, ak = I.keys[2]
     I.oracle_tags = en.oracle_raw(oracle, P, S, fk, ak, I.datas[2], w)
@@ -148,3 +165,46 @@ def test_six_calls_share_one_context(nat, inputs):
         for i in range(n):
             assert got[i] == I.want[call][i % 3], (step, call, i)
         singles_still_right(nat, I, (step, call))
+
+
+# ------------------------------------------------------------------ one prime and many owners, interleaved
+# The one-prime and the many-owner prove and verify calls fill their groups'
+# tables with the same code (hb_pv_host.hpp) over the same arena and staging
+# buffer.  The many-owner calls' items alternate between this file's prime with
+# S = 3 and P255 (ss 31, tw 32) with S = 2, so result columns and alpha slots
+# are ragged.
+PV_CALLS = ["prove", "prove_mixed", "verify", "verify_mixed", "cxx_prove", "cxx_prove_mixed", "cxx_verify", "cxx_verify_mixed"]
+MIXED = {"prove_mixed": pm.prove_mixed, "verify_mixed": vm.verify_mixed, "cxx_prove_mixed": cpm.cm_prove,
+         "cxx_verify_mixed": cvm.cm_verify}
+
+
+@pytest.fixture(scope="module")
+def owners(nat, inputs):
+    """The two owners of the many-owner calls, each with its single calls' results from a fresh context."""
+    return [inputs, fresh_singles(nat, Inputs(nat, P255, 2, seed=20261))]
+
+
+def run_pv(nat, owners, call, n):
+    """One call of n items: (its results, what the single calls give), one per item."""
+    if call not in MIXED:
+        return run(nat, owners[0], call, n), [owners[0].want[call][i % 3] for i in range(n)]
+    base = call[:-len("_mixed")]
+    items, want = [], []
+    for k in range(n):
+        I = owners[k % 2]
+        it = I.items(base, 3)[k % 3]
+        items.append((I.p, I.S, it) if base.startswith("cxx") else (I.p, I.S) + it)
+        want.append(I.want[base][k % 3])
+    rc, got, _ = MIXED[call](nat, items)
+    assert rc == 0, (call, pr.last_error(nat))
+    return got, want
+
+
+def test_one_prime_and_many_owner_calls_interleaved(nat, inputs, owners):
+    order = [(call, 3) for call in PV_CALLS] + [(call, 40 if k == 0 else 3) for k, call in enumerate(reversed(PV_CALLS))]
+    for step, (call, n) in enumerate(order):
+        got, want = run_pv(nat, owners, call, n)
+        assert len(got) == n
+        for i in range(n):
+            assert got[i] == want[i], (step, call, i)
+        singles_still_right(nat, inputs, (step, call))
