@@ -22,6 +22,9 @@ HB_EUNSUPPORTED = -4
 HB_PRF_CXX = 8
 HB_ASYNC = 16
 HB_HOST_REGISTER = 32
+HB_MERKLE_CHAIN_HOST = 64
+HB_MERKLE_CHAIN_DEVICE = 128
+HB_MERKLE_MAX_N = 65536
 HB_BUILD_EXPERIMENT = 1
 HB_BUILD_TEST_SWITCHES = 2
 
@@ -78,6 +81,24 @@ class VerifyMixedDesc(ctypes.Structure):
     call, under its own prime, sector count and key lengths; then hb_verify_desc's words."""
     _fields_ = [("p_be", ctypes.c_char_p), ("p_len", ctypes.c_uint64), ("sectors", ctypes.c_uint64),
                 ("key_len", ctypes.c_uint64), ("chal_key_len", ctypes.c_uint64)] + VerifyDesc._fields_
+
+
+class MerkleEncodeDesc(ctypes.Structure):
+    """hb_merkle_encode_desc (hbswizzle.h): one file of an hb_merkle_encode_many call."""
+    _fields_ = [("key", ctypes.c_char_p), ("key_len", ctypes.c_uint64),
+                ("seed", ctypes.c_char_p), ("seed_len", ctypes.c_uint64),
+                ("n", ctypes.c_uint64), ("filesz", ctypes.c_uint64), ("chunksz", ctypes.c_uint64),
+                ("data", ctypes.c_void_p), ("len", ctypes.c_uint64),
+                ("nodes_out", ctypes.c_void_p), ("leaves_out", ctypes.c_void_p),
+                ("offsets_out", ctypes.c_void_p)]
+
+
+class MerkleLeafDesc(ctypes.Structure):
+    """hb_merkle_leaf_desc (hbswizzle.h): one proof of an hb_merkle_leaves_many call."""
+    _fields_ = [("seed", ctypes.c_char_p), ("seed_len", ctypes.c_uint64),
+                ("filesz", ctypes.c_uint64), ("chunksz", ctypes.c_uint64),
+                ("data", ctypes.c_void_p), ("len", ctypes.c_uint64),
+                ("leaf_out", ctypes.c_void_p), ("offset_out", ctypes.c_void_p)]
 
 
 SIGNATURES = [
@@ -154,6 +175,8 @@ SIGNATURES = [
     ("hb_merkle_offsets", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint64, _c.c_uint64, _c.c_uint64, _P]),
     ("hb_merkle_chunk_hmacs", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint64, _P, _c.c_uint64, _P,
                                          _c.c_uint64, _P]),
+    ("hb_merkle_encode_many", _c.c_int, [_P, _c.POINTER(MerkleEncodeDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_merkle_leaves_many", _c.c_int, [_P, _c.POINTER(MerkleLeafDesc), _c.c_uint64, _c.c_uint32]),
 ]
 
 

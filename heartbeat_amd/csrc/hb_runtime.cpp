@@ -41,6 +41,7 @@
 #include "hb_pv_host.hpp"
 #include "hb_emixed_host.hpp"
 #include "hb_prime_host.hpp"
+#include "hb_merkle_host.hpp"
 
 using namespace hbhost;
 
@@ -91,6 +92,11 @@ template <int NL> hipError_t hb_launch_emixed_mac(const EmMacArgs<NL> &, u32, u3
 // hb_prime.hpp (hb_kern_prime*.hip)
 template <int NL> hipError_t hb_launch_prime_test(const PrTestArgs &, bool, hipStream_t);
 template <int NL> hipError_t hb_launch_prime_sieve(const PrSieveArgs &, u32, u32, hipStream_t);
+
+// hb_kern_merkle.hip
+hipError_t hb_launch_merkle_chain(const MkChainArgs &, hipStream_t);
+hipError_t hb_launch_merkle_leaves(const MkLeavesArgs &, int, hipStream_t);
+hipError_t hb_launch_merkle_tree(const MkTreeArgs &, u64, hipStream_t);
 
 namespace {
 
@@ -177,6 +183,11 @@ struct hb_ctx {
     // primes (written once: pr_q_n), windows, survivors and counts
     DevBuf pr_src, pr_bases, pr_jobs, pr_pass, pr_q, pr_win, pr_surv, pr_cnt;
     u32 pr_q_n = 0;
+    // hb_merkle_encode_many / hb_merkle_leaves_many: the file table, the seeds,
+    // positions, leaf blobs and nodes of a batch, the uploaded host files and
+    // the gathered chunks; their pinned staging (results, positions)
+    DevBuf mk_files, mk_seeds, mk_offs, mk_blobs, mk_nodes, mk_data, mk_gather;
+    HostBuf mk_out;
     HostBuf hscratch;    // pinned staging of the encode's small host round trips (alpha, MFMA tables)
     // the alpha D2H into hscratch done / the MFMA-table H2D out of it done
     // (not yet waited for: the next round trip must wait before reusing hscratch)
@@ -3950,13 +3961,16 @@ void hb_ctx_destroy(hb_ctx *c) {
                       &c->partials, &c->sums, &c->data[0], &c->data[1], &c->tags, &c->blen, &c->gtags,
                       &c->pfx, &c->retry, &c->ctl, &c->afrag, &c->mseeds, &c->moffs, &c->mdig, &c->gdev,
                       &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig, &c->bdev, &c->pr_src, &c->pr_bases,
-                      &c->pr_jobs, &c->pr_pass, &c->pr_q, &c->pr_win, &c->pr_surv, &c->pr_cnt};
+                      &c->pr_jobs, &c->pr_pass, &c->pr_q, &c->pr_win, &c->pr_surv, &c->pr_cnt,
+                      &c->mk_files, &c->mk_seeds, &c->mk_offs, &c->mk_blobs, &c->mk_nodes, &c->mk_data,
+                      &c->mk_gather};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
     c->gstage[1].release();
     c->hscratch.release();
     c->bhost.release();
+    c->mk_out.release();
     if (c->t0) (void)hipFree(c->t0);
     if (c->queue) (void)hipFree(c->queue);
     if (c->k0) (void)hipEventDestroy(c->k0);
@@ -4981,6 +4995,248 @@ int hb_merkle_chunk_hmacs(hb_ctx *c, const uint8_t *seeds, size_t seed_len, uint
     HB_CHECK(hipStreamSynchronize(c->stream), "hb_hmac_kernel");
     for (size_t k = 0; k < h.size(); ++k)
         for (int b = 0; b < 4; ++b) digests[4 * k + b] = (uint8_t)(h[k] >> (24 - 8 * b));
+    return 0;
+}
+
+// ------------------------------------------------------------------ Merkle scheme
+namespace {
+
+struct MkSrc {
+    const uint8_t *data;   // the caller's bytes (host, or device with HB_DATA_ON_DEVICE)
+    u64 filesz;
+};
+
+// a run of jobs whose seeds have one length
+struct MkRun {
+    u64 lo, hi;
+    int nr;
+};
+
+// The launches of a planned batch.  P.files is complete but for the data
+// pointers; host_seeds (jobs x 32 bytes) or, when NULL, the device chain fills
+// the seeds.  Leaves c->mk_out holding nodes | blobs | positions, synchronised.
+int merkle_run(hb_ctx *c, MkPlan &P, const std::vector<MkSrc> &src, bool data_dev, const uint8_t *host_seeds,
+               bool want_nodes, const std::vector<MkRun> &runs) {
+    const size_t nfiles = P.files.size();
+    const size_t jobs = (size_t)P.jobs;
+    if (P.jobs > (1ull << 31)) return fail(c, HB_EUNSUPPORTED, "more than 2^31 Merkle leaves in one call");
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    if (int rc = ensure_ctl(c, 1)) return rc;
+    // where every file's bytes are
+    bool any_gather = false;
+    size_t up_bytes = 0;
+    std::vector<size_t> up_at(nfiles, 0);
+    for (size_t i = 0; i < nfiles; ++i) {
+        MkFile &F = P.files[i];
+        if (data_dev) {
+            F.data = src[i].data;
+            F.len = src[i].filesz;
+        } else if (src[i].filesz > mk_upload_max(F.n, F.chunk)) {
+            F.flags |= HB_MK_GATHER;
+            any_gather = true;
+        } else {
+            up_at[i] = up_bytes;
+            up_bytes += ((size_t)src[i].filesz + 15) & ~(size_t)15;
+        }
+    }
+    const size_t node_bytes = want_nodes ? (size_t)P.nodes * 32 : 0;
+    HB_CHECK(c->mk_files.ensure(nfiles * sizeof(MkFile)), "hipMalloc");
+    HB_CHECK(c->mk_seeds.ensure(jobs * 32), "hipMalloc");
+    HB_CHECK(c->mk_offs.ensure(jobs * 8), "hipMalloc");
+    HB_CHECK(c->mk_blobs.ensure(jobs * 32), "hipMalloc");
+    HB_CHECK(c->mk_nodes.ensure(node_bytes), "hipMalloc");
+    HB_CHECK(c->mk_data.ensure(up_bytes), "hipMalloc");
+    HB_CHECK(c->mk_out.ensure(node_bytes + jobs * 40), "hipHostMalloc");
+    if (!data_dev)
+        for (size_t i = 0; i < nfiles; ++i) {
+            MkFile &F = P.files[i];
+            if (F.flags & HB_MK_GATHER) continue;
+            F.data = (const unsigned char *)c->mk_data.p + up_at[i];
+            F.len = src[i].filesz;
+            if (src[i].filesz)
+                HB_CHECK(hipMemcpyAsync((void *)F.data, src[i].data, (size_t)src[i].filesz, hipMemcpyHostToDevice,
+                                        c->stream), "H2D");
+        }
+    HB_CHECK(hipMemcpyAsync(c->mk_files.p, P.files.data(), nfiles * sizeof(MkFile), hipMemcpyHostToDevice,
+                            c->stream), "H2D");
+    unsigned int *flw = flags_word(c);
+    HB_CHECK(hipMemsetAsync(flw, 0, 4, c->stream), "hipMemsetAsync");
+    if (want_nodes) HB_CHECK(hipMemsetAsync(c->mk_nodes.p, 0, node_bytes, c->stream), "hipMemsetAsync");
+    HB_CHECK(hipEventRecord(c->k0, c->stream), "hipEventRecord");
+    if (host_seeds) {
+        HB_CHECK(hipMemcpyAsync(c->mk_seeds.p, host_seeds, jobs * 32, hipMemcpyHostToDevice, c->stream), "H2D");
+    } else {
+        MkChainArgs CA = {(const MkFile *)c->mk_files.p, (u64)nfiles, (u32 *)c->mk_seeds.p};
+        HB_CHECK(hb_launch_merkle_chain(CA, c->stream), "hb_merkle_chain_kernel launch");
+    }
+    HB_CHECK(hipEventRecord(c->ph[0], c->stream), "hipEventRecord");
+    MkLeavesArgs A;
+    memset(&A, 0, sizeof A);
+    A.files = (const MkFile *)c->mk_files.p;
+    A.nfiles = nfiles;
+    A.seeds = (const u32 *)c->mk_seeds.p;
+    A.offsets = (u64 *)c->mk_offs.p;
+    A.blobs = (u32 *)c->mk_blobs.p;
+    A.nodes = want_nodes ? (u32 *)c->mk_nodes.p : nullptr;
+    // SHA-256("0"): eval(0) hashes str(0) (util.py:91)
+    static const u32 dig0[8] = {0x5feceb66u, 0xffc86f38u, 0xd952786cu, 0x6d696c79u,
+                                0xc2dbc239u, 0xdd4e91b4u, 0x6729d73au, 0x27fb57e9u};
+    memcpy(A.dig0, dig0, sizeof dig0);
+    A.flags = flw;
+    A.t0 = c->t0;
+    for (const MkRun &r : runs) {
+        A.job_lo = r.lo;
+        A.job_hi = r.hi;
+        if (r.hi > r.lo) HB_CHECK(hb_launch_merkle_leaves(A, r.nr, c->stream), "hb_merkle_leaves_kernel launch");
+    }
+    uint8_t *out = (uint8_t *)c->mk_out.p;
+    u64 *offs_h = (u64 *)(out + node_bytes + jobs * 32);
+    u32 fl = 0;
+    auto finish_flags = [&]() -> int {
+        HB_CHECK(hipMemcpyAsync(&fl, flw, 4, hipMemcpyDeviceToHost, c->stream), "D2H");
+        HB_CHECK(hipMemsetAsync(flw, 0, 4, c->stream), "hipMemsetAsync");   // zero between operations
+        HB_CHECK(hipStreamSynchronize(c->stream), "hb_merkle_leaves_kernel");
+        if (fl & 2u) return fail(c, HB_EINVAL, "PRF rejection sampling did not terminate");
+        if (fl & 4u) return fail(c, HB_EINVAL, "chunk past the end of the data");
+        return 0;
+    };
+    std::vector<uint8_t> stage;   // the gathered chunks: alive until the last synchronise
+    if (any_gather) {
+        // the positions first; then only the chunks go up, leaf k of a file at k * chunk
+        HB_CHECK(hipMemcpyAsync(offs_h, c->mk_offs.p, jobs * 8, hipMemcpyDeviceToHost, c->stream), "D2H");
+        if (int rc = finish_flags()) return rc;
+        size_t g_bytes = 0;
+        std::vector<size_t> g_at(nfiles, 0);
+        for (size_t i = 0; i < nfiles; ++i)
+            if (P.files[i].flags & HB_MK_GATHER) {
+                g_at[i] = g_bytes;
+                g_bytes += ((size_t)P.files[i].n * (size_t)P.files[i].chunk + 15) & ~(size_t)15;
+            }
+        stage.resize(g_bytes);
+        HB_CHECK(c->mk_gather.ensure(g_bytes), "hipMalloc");
+        for (size_t i = 0; i < nfiles; ++i) {
+            MkFile &F = P.files[i];
+            if (!(F.flags & HB_MK_GATHER)) continue;
+            for (u32 k = 0; k < F.n; ++k) {
+                const u64 at = offs_h[F.job0 + k];
+                if (at > src[i].filesz || src[i].filesz - at < F.chunk)
+                    return fail(c, HB_EINVAL, "chunk past the end of the data");
+                memcpy(stage.data() + g_at[i] + (size_t)k * (size_t)F.chunk, src[i].data + at, (size_t)F.chunk);
+            }
+            F.data = (const unsigned char *)c->mk_gather.p + g_at[i];
+            F.len = (u64)F.n * F.chunk;
+        }
+        HB_CHECK(hipMemcpyAsync(c->mk_gather.p, stage.data(), g_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
+        HB_CHECK(hipMemcpyAsync(c->mk_files.p, P.files.data(), nfiles * sizeof(MkFile), hipMemcpyHostToDevice,
+                                c->stream), "H2D");
+        A.pass = 1;
+        for (const MkRun &r : runs) {
+            A.job_lo = r.lo;
+            A.job_hi = r.hi;
+            if (r.hi > r.lo) HB_CHECK(hb_launch_merkle_leaves(A, r.nr, c->stream), "hb_merkle_leaves_kernel launch");
+        }
+    }
+    HB_CHECK(hipEventRecord(c->ph[1], c->stream), "hipEventRecord");
+    if (want_nodes) {
+        MkTreeArgs TA = {(const MkFile *)c->mk_files.p, (u32 *)c->mk_nodes.p};
+        HB_CHECK(hb_launch_merkle_tree(TA, nfiles, c->stream), "hb_merkle_tree_kernel launch");
+    }
+    HB_CHECK(hipEventRecord(c->ph[2], c->stream), "hipEventRecord");
+    if (node_bytes) HB_CHECK(hipMemcpyAsync(out, c->mk_nodes.p, node_bytes, hipMemcpyDeviceToHost, c->stream), "D2H");
+    HB_CHECK(hipMemcpyAsync(out + node_bytes, c->mk_blobs.p, jobs * 32, hipMemcpyDeviceToHost, c->stream), "D2H");
+    HB_CHECK(hipMemcpyAsync(offs_h, c->mk_offs.p, jobs * 8, hipMemcpyDeviceToHost, c->stream), "D2H");
+    HB_CHECK(hipEventRecord(c->k1, c->stream), "hipEventRecord");
+    if (int rc = finish_flags()) return rc;
+    // the phases of hb_last_kernel_phases: chain, leaves, trees, copies back
+    c->ph_valid = want_nodes && !any_gather;
+    return 0;
+}
+
+}  // namespace
+
+int hb_merkle_encode_many(hb_ctx *c, const hb_merkle_encode_desc *files, uint64_t nfiles, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    const u32 chain = flags & (HB_MERKLE_CHAIN_HOST | HB_MERKLE_CHAIN_DEVICE);
+    if ((flags & ~(HB_DATA_ON_DEVICE | HB_MERKLE_CHAIN_HOST | HB_MERKLE_CHAIN_DEVICE)) ||
+        chain == (HB_MERKLE_CHAIN_HOST | HB_MERKLE_CHAIN_DEVICE))
+        return fail(c, HB_EINVAL, "hb_merkle_encode_many: unsupported flags");
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "NULL buffer");
+    c->ph_valid = false;
+    MkPlan P;
+    int code = 0;
+    std::string err;
+    if (!mk_plan_encode(files, nfiles, P, code, err)) return fail(c, code, err);
+    std::vector<MkSrc> src((size_t)nfiles);
+    for (size_t i = 0; i < (size_t)nfiles; ++i) src[i] = {files[i].data, files[i].filesz};
+    const bool host_chain = chain ? chain == HB_MERKLE_CHAIN_HOST : nfiles < MK_CHAIN_DEVICE_MIN_FILES;
+    std::vector<uint8_t> seeds;
+    if (host_chain) {
+        seeds.resize((size_t)P.jobs * 32);
+        for (size_t i = 0; i < (size_t)nfiles; ++i) mk_host_chain(P.files[i], seeds.data() + (size_t)P.files[i].job0 * 32);
+    }
+    const std::vector<MkRun> runs = {{0, P.jobs, 14}};
+    if (int rc = merkle_run(c, P, src, (flags & HB_DATA_ON_DEVICE) != 0, host_chain ? seeds.data() : nullptr, true,
+                            runs))
+        return rc;
+    const uint8_t *out = (const uint8_t *)c->mk_out.p;
+    const uint8_t *blobs = out + (size_t)P.nodes * 32;
+    const u64 *offs = (const u64 *)(blobs + (size_t)P.jobs * 32);
+    for (size_t i = 0; i < (size_t)nfiles; ++i) {
+        const MkFile &F = P.files[i];
+        memcpy(files[i].nodes_out, out + (size_t)F.node0 * 32, (size_t)(2ull << F.order) * 32);
+        if (files[i].leaves_out) memcpy(files[i].leaves_out, blobs + (size_t)F.job0 * 32, (size_t)F.n * 32);
+        if (files[i].offsets_out) memcpy(files[i].offsets_out, offs + F.job0, (size_t)F.n * 8);
+    }
+    return 0;
+}
+
+int hb_merkle_leaves_many(hb_ctx *c, const hb_merkle_leaf_desc *proofs, uint64_t nproofs, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (flags & ~HB_DATA_ON_DEVICE) return fail(c, HB_EINVAL, "hb_merkle_leaves_many: unsupported flags");
+    if (nproofs == 0) return 0;
+    if (!proofs) return fail(c, HB_EINVAL, "NULL buffer");
+    c->ph_valid = false;
+    // the proofs by seed length: a launch per length (its AES round count)
+    std::vector<size_t> order;
+    order.reserve((size_t)nproofs);
+    std::vector<MkRun> runs;
+    for (size_t sl = 16; sl <= 32; sl += 8) {
+        const u64 lo = order.size();
+        for (size_t i = 0; i < (size_t)nproofs; ++i)
+            if (proofs[i].seed_len == sl) order.push_back(i);
+        runs.push_back({lo, (u64)order.size(), sl == 16 ? 10 : sl == 24 ? 12 : 14});
+    }
+    if (order.size() != (size_t)nproofs) return fail(c, HB_EINVAL, "AES key must be either 16, 24, or 32 bytes long");
+    MkPlan P;
+    P.files.assign((size_t)nproofs, MkFile());
+    std::vector<MkSrc> src((size_t)nproofs);
+    std::vector<uint8_t> seeds((size_t)nproofs * 32, 0);
+    for (size_t j = 0; j < order.size(); ++j) {
+        const hb_merkle_leaf_desc &d = proofs[order[j]];
+        MkFile &F = P.files[j];
+        memset(&F, 0, sizeof F);
+        if (!d.seed || !d.leaf_out || (!d.data && d.filesz)) return fail(c, HB_EINVAL, "NULL buffer");
+        int code = 0;
+        std::string err;
+        if (!mk_fill_range(F, d.filesz, d.chunksz, d.len, code, err)) return fail(c, code, err);
+        F.n = 1;
+        F.seed_len = (u32)d.seed_len;
+        F.job0 = j;
+        memcpy(seeds.data() + j * 32, d.seed, (size_t)d.seed_len);
+        src[j] = {d.data, d.filesz};
+    }
+    P.jobs = nproofs;
+    if (int rc = merkle_run(c, P, src, (flags & HB_DATA_ON_DEVICE) != 0, seeds.data(), false, runs)) return rc;
+    const uint8_t *blobs = (const uint8_t *)c->mk_out.p;
+    const u64 *offs = (const u64 *)(blobs + (size_t)nproofs * 32);
+    for (size_t j = 0; j < order.size(); ++j) {
+        const hb_merkle_leaf_desc &d = proofs[order[j]];
+        memcpy(d.leaf_out, blobs + j * 32, 32);
+        if (d.offset_out) *d.offset_out = offs[j];
+    }
     return 0;
 }
 

@@ -235,6 +235,72 @@ int hb_merkle_chunk_hmacs(hb_ctx *ctx, const uint8_t *seeds, size_t seed_len, ui
                           const uint8_t *data_dev, uint64_t len, const uint64_t *offsets,
                           uint64_t chunk_len, uint8_t *digests);
 
+/* Merkle encode of many files in one call.
+ * Replaces heartbeat/Merkle/Merkle.py:355-364 (Merkle.encode's seed chain,
+ * its n get_chunk_hash calls and MerkleTree.build) for nfiles files, each
+ * under its own key, seed, n and chunk size (one owner's files, or many
+ * owners').  With chunk = min(chunksz, filesz) (Merkle.py:500-501),
+ * s_1 = HMAC-SHA256(key, seed), s_{k+1} = HMAC-SHA256(key, s_k):
+ *   offsets_out[k] = KeyedPRF(s_{k+1}, filesz - chunk + 1).eval(0)
+ *   leaves_out[k]  = HMAC-SHA256(s_{k+1}, data[offsets_out[k] : +chunk])
+ *   nodes_out      = the tree's (2 << order) nodes of 32 bytes each in the
+ *                    reference's numbering (MerkleTree.py:29-36), node
+ *                    2^order - 1 + k = SHA-256(leaf k || decimal(k)), empty
+ *                    slots (leaf slots >= n, the last entry) all zero;
+ *                    order = 0 for n = 1, else the bit length of n - 1.
+ * Three launches serve the whole batch: the seed chains (a lane per file; on
+ * the host for a few files), the leaves (a lane per leaf) and the trees (a
+ * workgroup per file).  A host file of more than max(2 n chunk, 8 MiB) bytes
+ * is not uploaded: its positions come back first and only its chunks go up.
+ * flags: HB_DATA_ON_DEVICE (every `data` is a device pointer), and at most
+ * one of HB_MERKLE_CHAIN_HOST / HB_MERKLE_CHAIN_DEVICE to force where the
+ * chains run; anything else returns HB_EINVAL.  Every descriptor is checked
+ * before the first launch: 1 <= n <= 65536, filesz <= len ("chunk past the
+ * end of the data"), no NULL buffer; a range filesz - chunk + 1 of 2^64 is
+ * HB_EUNSUPPORTED.  nfiles = 0 is a no-op.  After a call in which no file was
+ * gathered, hb_last_kernel_phases reports its four phases: the chains (or the
+ * upload of the host's seeds), the leaves, the trees, the copies back. */
+#define HB_MERKLE_CHAIN_HOST 64u
+#define HB_MERKLE_CHAIN_DEVICE 128u
+#define HB_MERKLE_MAX_N 65536u
+typedef struct hb_merkle_encode_desc {
+    const uint8_t *key;      /* the owner's HMAC key, key_len bytes (may be NULL when key_len == 0) */
+    uint64_t key_len;
+    const uint8_t *seed;     /* the state seed, seed_len bytes of any length */
+    uint64_t seed_len;
+    uint64_t n;              /* leaves (challenges) */
+    uint64_t filesz;         /* the size the positions are drawn for; <= len */
+    uint64_t chunksz;
+    const uint8_t *data;     /* host, or device with HB_DATA_ON_DEVICE; may be NULL when filesz == 0 */
+    uint64_t len;            /* readable bytes at data */
+    uint8_t *nodes_out;      /* host, (2 << order) * 32 bytes */
+    uint8_t *leaves_out;     /* host, n * 32 bytes, or NULL */
+    uint64_t *offsets_out;   /* host, n positions, or NULL */
+} hb_merkle_encode_desc;
+int hb_merkle_encode_many(hb_ctx *ctx, const hb_merkle_encode_desc *files, uint64_t nfiles,
+                          uint32_t flags);
+
+/* Merkle leaves of many proofs in one call (the prove side, Merkle.py:399-403).
+ * Proof i, under its own seed (16, 24 or 32 bytes), file and range:
+ *   offset_out = KeyedPRF(seed, filesz - chunk + 1).eval(0), chunk = min(chunksz, filesz)
+ *   leaf_out   = HMAC-SHA256(seed, data[offset : offset + chunk])   (32 bytes)
+ * A lane per proof.  Host files are uploaded or gathered as in
+ * hb_merkle_encode_many (n = 1).  flags: HB_DATA_ON_DEVICE or 0.  Checked
+ * before the first launch: filesz <= len, the seed length, no NULL buffer
+ * (offset_out may be NULL). */
+typedef struct hb_merkle_leaf_desc {
+    const uint8_t *seed;
+    uint64_t seed_len;
+    uint64_t filesz;
+    uint64_t chunksz;
+    const uint8_t *data;     /* host, or device with HB_DATA_ON_DEVICE; may be NULL when filesz == 0 */
+    uint64_t len;
+    uint8_t *leaf_out;
+    uint64_t *offset_out;
+} hb_merkle_leaf_desc;
+int hb_merkle_leaves_many(hb_ctx *ctx, const hb_merkle_leaf_desc *proofs, uint64_t nproofs,
+                          uint32_t flags);
+
 /* Swizzle encode of a run of blocks.
  * Replaces heartbeat/PySwizzle/PySwizzle.py:296-309 (the encode loop) and
  * cxx/shacham_waters_private.cxx:672-697.  For k in [0, nblocks):
