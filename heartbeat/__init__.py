@@ -13,8 +13,11 @@ defines: this package holds no logic of its own.  Classes carry the
 reference's module paths (``heartbeat.PySwizzle.PySwizzle.Tag``,
 ``heartbeat.Swizzle.State``, ``heartbeat.exc.HeartbeatError`` ...), so pickles
 name ``heartbeat.*`` and ``except heartbeat.exc.HeartbeatError`` catches every
-error the library raises.  The Merkle tree scheme and OneHash stay outside
-this build's scope; ``heartbeat.Merkle`` carries MerkleHelper.
+error the library raises.  ``heartbeat.Merkle`` carries MerkleHelper; the
+Merkle tree scheme is reached as ``heartbeat_amd.Merkle`` and is not
+re-exported here.  ``heartbeat.OneHash`` is the OneHash
+scheme (``heartbeat_amd.OneHash``); as in the reference, this module does not
+import it.
 """
 __version__ = "0.1.4"
 

@@ -25,6 +25,9 @@ HB_HOST_REGISTER = 32
 HB_MERKLE_CHAIN_HOST = 64
 HB_MERKLE_CHAIN_DEVICE = 128
 HB_MERKLE_MAX_N = 65536
+HB_ONEHASH_CHAIN_HOST = 64
+HB_ONEHASH_CHAIN_DEVICE = 128
+HB_ONEHASH_MAX_SEED_LEN = 64
 HB_BUILD_EXPERIMENT = 1
 HB_BUILD_TEST_SWITCHES = 2
 
@@ -99,6 +102,28 @@ class MerkleLeafDesc(ctypes.Structure):
                 ("filesz", ctypes.c_uint64), ("chunksz", ctypes.c_uint64),
                 ("data", ctypes.c_void_p), ("len", ctypes.c_uint64),
                 ("leaf_out", ctypes.c_void_p), ("offset_out", ctypes.c_void_p)]
+
+
+class OneHashGenDesc(ctypes.Structure):
+    """hb_onehash_gen_desc (hbswizzle.h): one file of an hb_onehash_generate_many call."""
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64), ("s0", ctypes.c_char_p),
+                ("secret", ctypes.c_char_p), ("secret_len", ctypes.c_uint64),
+                ("num", ctypes.c_uint64), ("blocks", ctypes.c_void_p)]
+
+
+class OneHashFile(ctypes.Structure):
+    """hb_onehash_file (hbswizzle.h): one file of an hb_onehash_meet_many call."""
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class OneHashJob(ctypes.Structure):
+    """hb_onehash_job (hbswizzle.h): one challenge of an hb_onehash_meet_many
+    call.  ONEHASH_JOB_DTYPE is the same record as a numpy dtype."""
+    _fields_ = [("file", ctypes.c_uint64), ("block", ctypes.c_uint64), ("seed_len", ctypes.c_uint64),
+                ("seed", ctypes.c_uint8 * 64)]
+
+
+ONEHASH_JOB_DTYPE = [("file", "<u8"), ("block", "<u8"), ("seed_len", "<u8"), ("seed", "u1", (64,))]
 
 
 SIGNATURES = [
@@ -177,6 +202,10 @@ SIGNATURES = [
                                          _c.c_uint64, _P]),
     ("hb_merkle_encode_many", _c.c_int, [_P, _c.POINTER(MerkleEncodeDesc), _c.c_uint64, _c.c_uint32]),
     ("hb_merkle_leaves_many", _c.c_int, [_P, _c.POINTER(MerkleLeafDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_onehash_generate_many", _c.c_int, [_P, _c.POINTER(OneHashGenDesc), _c.c_uint64, _P, _P, _c.c_uint32]),
+    ("hb_onehash_meet_many", _c.c_int, [_P, _c.POINTER(OneHashFile), _c.c_uint64, _P, _c.c_uint64, _P,
+                                        _c.c_uint32]),
+    ("hb_onehash_device_min_jobs", _c.c_uint64, []),
 ]
 
 

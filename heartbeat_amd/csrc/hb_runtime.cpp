@@ -42,6 +42,7 @@
 #include "hb_emixed_host.hpp"
 #include "hb_prime_host.hpp"
 #include "hb_merkle_host.hpp"
+#include "hb_onehash_host.hpp"
 
 using namespace hbhost;
 
@@ -97,6 +98,9 @@ template <int NL> hipError_t hb_launch_prime_sieve(const PrSieveArgs &, u32, u32
 hipError_t hb_launch_merkle_chain(const MkChainArgs &, hipStream_t);
 hipError_t hb_launch_merkle_leaves(const MkLeavesArgs &, int, hipStream_t);
 hipError_t hb_launch_merkle_tree(const MkTreeArgs &, u64, hipStream_t);
+// hb_kern_onehash.hip
+hipError_t hb_launch_onehash_chain(const OhChainArgs &, hipStream_t);
+hipError_t hb_launch_onehash_resp(const OhRespArgs &, hipStream_t);
 
 namespace {
 
@@ -188,6 +192,11 @@ struct hb_ctx {
     // the gathered chunks; their pinned staging (results, positions)
     DevBuf mk_files, mk_seeds, mk_offs, mk_blobs, mk_nodes, mk_data, mk_gather;
     HostBuf mk_out;
+    // hb_onehash_generate_many / hb_onehash_meet_many: the file table, the
+    // blocks or job records, the seeds and responses of a batch, the uploaded
+    // host files and the gathered segments; their pinned staging (results)
+    DevBuf oh_files, oh_jobs, oh_seeds, oh_resp, oh_data, oh_gather;
+    HostBuf oh_out;
     HostBuf hscratch;    // pinned staging of the encode's small host round trips (alpha, MFMA tables)
     // the alpha D2H into hscratch done / the MFMA-table H2D out of it done
     // (not yet waited for: the next round trip must wait before reusing hscratch)
@@ -3963,7 +3972,8 @@ void hb_ctx_destroy(hb_ctx *c) {
                       &c->facc, &c->gup, &c->wpw, &c->wtab, &c->dig, &c->bdev, &c->pr_src, &c->pr_bases,
                       &c->pr_jobs, &c->pr_pass, &c->pr_q, &c->pr_win, &c->pr_surv, &c->pr_cnt,
                       &c->mk_files, &c->mk_seeds, &c->mk_offs, &c->mk_blobs, &c->mk_nodes, &c->mk_data,
-                      &c->mk_gather};
+                      &c->mk_gather, &c->oh_files, &c->oh_jobs, &c->oh_seeds, &c->oh_resp, &c->oh_data,
+                      &c->oh_gather};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
@@ -3971,6 +3981,7 @@ void hb_ctx_destroy(hb_ctx *c) {
     c->hscratch.release();
     c->bhost.release();
     c->mk_out.release();
+    c->oh_out.release();
     if (c->t0) (void)hipFree(c->t0);
     if (c->queue) (void)hipFree(c->queue);
     if (c->k0) (void)hipEventDestroy(c->k0);
@@ -5239,6 +5250,219 @@ int hb_merkle_leaves_many(hb_ctx *c, const hb_merkle_leaf_desc *proofs, uint64_t
     }
     return 0;
 }
+
+// ------------------------------------------------------------------ OneHash scheme
+namespace {
+
+struct OhSrc {
+    const uint8_t *data;   // the caller's bytes (host, or device with HB_DATA_ON_DEVICE)
+    u64 len;
+};
+
+// What the response kernel reads per job, on the host: the sorted blocks (for
+// the gather), and the arrays as they go to the device.
+struct OhJobs {
+    const uint8_t *rec;        // the job array uploaded to oh_jobs: rec_bytes in all
+    size_t rec_bytes;
+    u64 block_off, block_stride;   // job j's block at rec + block_off + j * block_stride
+    bool own_seeds;            // the seeds and their lengths are in rec (the meet side)
+    u64 seed_off, len_off;
+};
+
+// The launches of a planned batch.  P.files is complete but for the data
+// pointers.  Generate side: host_seeds (jobs x 32 bytes) when the host walked
+// every chain, else the device chain fills the seeds, after the slices of
+// files with HB_OH_HOST_CHAIN came up from host_long.  Leaves c->oh_out
+// holding responses | seeds (the generate side), synchronised.
+int onehash_run(hb_ctx *c, OhPlan &P, const std::vector<OhSrc> &src, bool data_dev, const OhJobs &J,
+                const uint8_t *host_seeds, const uint8_t *host_long) {
+    const size_t nfiles = P.files.size();
+    const size_t jobs = (size_t)P.jobs;
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    if (int rc = ensure_ctl(c, 1)) return rc;
+    auto block_of = [&](u64 j) {
+        u64 b;
+        memcpy(&b, J.rec + J.block_off + j * J.block_stride, 8);
+        return b;
+    };
+    // where every file's bytes are
+    size_t up_bytes = 0, g_bytes = 0;
+    std::vector<size_t> at(nfiles, 0);
+    for (size_t i = 0; i < nfiles; ++i) {
+        OhFile &F = P.files[i];
+        if (data_dev) {
+            F.data = src[i].data;
+        } else if (F.n == 0) {
+            F.data = nullptr;   // no job reads it
+        } else if (src[i].len > oh_upload_max(F.n)) {
+            F.flags |= HB_OH_GATHER;
+            at[i] = g_bytes;
+            g_bytes += ((size_t)F.n * (size_t)hb_oh_chunk(F.file_size) + 15) & ~(size_t)15;
+        } else {
+            at[i] = up_bytes;
+            up_bytes += ((size_t)src[i].len + 15) & ~(size_t)15;
+        }
+    }
+    HB_CHECK(c->oh_files.ensure(nfiles * sizeof(OhFile)), "hipMalloc");
+    HB_CHECK(c->oh_jobs.ensure(J.rec_bytes), "hipMalloc");
+    HB_CHECK(c->oh_seeds.ensure(jobs * 32), "hipMalloc");
+    HB_CHECK(c->oh_resp.ensure(jobs * 32), "hipMalloc");
+    HB_CHECK(c->oh_data.ensure(up_bytes), "hipMalloc");
+    HB_CHECK(c->oh_gather.ensure(g_bytes), "hipMalloc");
+    HB_CHECK(c->oh_out.ensure(jobs * 64), "hipHostMalloc");
+    std::vector<uint8_t> stage(g_bytes);   // the gathered segments: alive until the synchronise
+    if (!data_dev)
+        for (size_t i = 0; i < nfiles; ++i) {
+            OhFile &F = P.files[i];
+            if (F.n == 0) continue;
+            if (F.flags & HB_OH_GATHER) {
+                const size_t chunk = (size_t)hb_oh_chunk(F.file_size);
+                for (u32 k = 0; k < F.n; ++k)
+                    if (!oh_gather_job(src[i].data, src[i].len, block_of(F.job0 + k), stage.data() + at[i] + k * chunk))
+                        return fail(c, HB_EINVAL, "segment past the end of the data");
+                F.data = (const unsigned char *)c->oh_gather.p + at[i];
+                F.len = (u64)F.n * chunk;
+            } else {
+                F.data = (const unsigned char *)c->oh_data.p + at[i];
+                if (src[i].len)
+                    HB_CHECK(hipMemcpyAsync((void *)F.data, src[i].data, (size_t)src[i].len, hipMemcpyHostToDevice,
+                                            c->stream), "H2D");
+            }
+        }
+    if (g_bytes) HB_CHECK(hipMemcpyAsync(c->oh_gather.p, stage.data(), g_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
+    HB_CHECK(hipMemcpyAsync(c->oh_files.p, P.files.data(), nfiles * sizeof(OhFile), hipMemcpyHostToDevice,
+                            c->stream), "H2D");
+    HB_CHECK(hipMemcpyAsync(c->oh_jobs.p, J.rec, J.rec_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
+    unsigned int *flw = flags_word(c);
+    HB_CHECK(hipMemsetAsync(flw, 0, 4, c->stream), "hipMemsetAsync");
+    HB_CHECK(hipEventRecord(c->k0, c->stream), "hipEventRecord");
+    if (!J.own_seeds) {
+        if (host_seeds) {
+            HB_CHECK(hipMemcpyAsync(c->oh_seeds.p, host_seeds, jobs * 32, hipMemcpyHostToDevice, c->stream), "H2D");
+        } else {
+            for (size_t i = 0; i < nfiles; ++i) {
+                const OhFile &F = P.files[i];
+                if ((F.flags & HB_OH_HOST_CHAIN) && F.n)
+                    HB_CHECK(hipMemcpyAsync((uint8_t *)c->oh_seeds.p + (size_t)F.job0 * 32,
+                                            host_long + (size_t)F.job0 * 32, (size_t)F.n * 32,
+                                            hipMemcpyHostToDevice, c->stream), "H2D");
+            }
+            OhChainArgs CA = {(const OhFile *)c->oh_files.p, (u64)nfiles, (u32 *)c->oh_seeds.p};
+            HB_CHECK(hb_launch_onehash_chain(CA, c->stream), "hb_onehash_chain_kernel launch");
+        }
+    }
+    OhRespArgs A;
+    memset(&A, 0, sizeof A);
+    A.files = (const OhFile *)c->oh_files.p;
+    A.nfiles = nfiles;
+    A.njobs = jobs;
+    A.blocks = (const unsigned char *)c->oh_jobs.p + J.block_off;
+    A.block_stride = J.block_stride;
+    if (J.own_seeds) {
+        A.seeds = (const unsigned char *)c->oh_jobs.p + J.seed_off;
+        A.seed_lens = (const unsigned char *)c->oh_jobs.p + J.len_off;
+        A.seed_stride = A.len_stride = J.block_stride;
+    } else {
+        A.seeds = (const unsigned char *)c->oh_seeds.p;
+        A.seed_stride = 32;
+    }
+    A.resp = (u32 *)c->oh_resp.p;
+    A.flags = flw;
+    HB_CHECK(hb_launch_onehash_resp(A, c->stream), "hb_onehash_resp_kernel launch");
+    uint8_t *out = (uint8_t *)c->oh_out.p;
+    HB_CHECK(hipMemcpyAsync(out, c->oh_resp.p, jobs * 32, hipMemcpyDeviceToHost, c->stream), "D2H");
+    if (!J.own_seeds)
+        HB_CHECK(hipMemcpyAsync(out + jobs * 32, c->oh_seeds.p, jobs * 32, hipMemcpyDeviceToHost, c->stream), "D2H");
+    HB_CHECK(hipEventRecord(c->k1, c->stream), "hipEventRecord");
+    u32 fl = 0;
+    HB_CHECK(hipMemcpyAsync(&fl, flw, 4, hipMemcpyDeviceToHost, c->stream), "D2H");
+    HB_CHECK(hipMemsetAsync(flw, 0, 4, c->stream), "hipMemsetAsync");   // zero between operations
+    HB_CHECK(hipStreamSynchronize(c->stream), "hb_onehash_resp_kernel");
+    if (fl & 4u) return fail(c, HB_EINVAL, "segment past the end of the data");
+    return 0;
+}
+
+}  // namespace
+
+int hb_onehash_generate_many(hb_ctx *c, const hb_onehash_gen_desc *files, uint64_t nfiles, uint8_t *seeds_out,
+                             uint8_t *responses_out, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    const u32 chain = flags & (HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE);
+    if ((flags & ~(HB_DATA_ON_DEVICE | HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE)) ||
+        chain == (HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE))
+        return fail(c, HB_EINVAL, "hb_onehash_generate_many: unsupported flags");
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "NULL buffer");
+    c->ph_valid = false;
+    OhPlan P;
+    int code = 0;
+    std::string err;
+    if (!oh_plan_generate(files, nfiles, seeds_out, responses_out, P, code, err)) return fail(c, code, err);
+    if (P.jobs == 0) return 0;
+    const size_t jobs = (size_t)P.jobs;
+    std::vector<OhSrc> src((size_t)nfiles);
+    std::vector<u64> blocks(jobs);
+    for (size_t i = 0; i < (size_t)nfiles; ++i) {
+        src[i] = {files[i].data, files[i].len};
+        if (files[i].num) memcpy(blocks.data() + P.files[i].job0, files[i].blocks, (size_t)files[i].num * 8);
+    }
+    const bool host_chain = chain ? chain == HB_ONEHASH_CHAIN_HOST : nfiles < OH_CHAIN_DEVICE_MIN_FILES;
+    std::vector<uint8_t> seeds;
+    bool any_long = false;
+    for (const OhFile &F : P.files) any_long |= (F.flags & HB_OH_HOST_CHAIN) && F.n;
+    if (host_chain || any_long) {
+        seeds.resize(jobs * 32);
+        for (size_t i = 0; i < (size_t)nfiles; ++i)
+            if (host_chain || (P.files[i].flags & HB_OH_HOST_CHAIN))
+                oh_host_chain(P.files[i], files[i].secret, files[i].secret_len, seeds.data() + (size_t)P.files[i].job0 * 32);
+    }
+    OhJobs J;
+    memset(&J, 0, sizeof J);
+    J.rec = (const uint8_t *)blocks.data();
+    J.rec_bytes = jobs * 8;
+    J.block_stride = 8;
+    if (int rc = onehash_run(c, P, src, (flags & HB_DATA_ON_DEVICE) != 0, J, host_chain ? seeds.data() : nullptr,
+                             seeds.data()))
+        return rc;
+    const uint8_t *out = (const uint8_t *)c->oh_out.p;
+    memcpy(responses_out, out, jobs * 32);
+    memcpy(seeds_out, out + jobs * 32, jobs * 32);
+    return 0;
+}
+
+int hb_onehash_meet_many(hb_ctx *c, const hb_onehash_file *files, uint64_t nfiles, const hb_onehash_job *jobs,
+                         uint64_t njobs, uint8_t *responses_out, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (flags & ~HB_DATA_ON_DEVICE) return fail(c, HB_EINVAL, "hb_onehash_meet_many: unsupported flags");
+    if (njobs == 0) return 0;
+    c->ph_valid = false;
+    OhPlan P;
+    std::vector<size_t> order;
+    int code = 0;
+    std::string err;
+    if (!oh_plan_meet(files, nfiles, jobs, njobs, responses_out, P, order, code, err)) return fail(c, code, err);
+    std::vector<OhSrc> src((size_t)nfiles);
+    for (size_t i = 0; i < (size_t)nfiles; ++i) src[i] = {files[i].data, files[i].len};
+    std::vector<hb_onehash_job> sorted((size_t)njobs);
+    for (size_t j = 0; j < (size_t)njobs; ++j) sorted[j] = jobs[order[j]];
+    OhJobs J;
+    memset(&J, 0, sizeof J);
+    J.rec = (const uint8_t *)sorted.data();
+    J.rec_bytes = (size_t)njobs * sizeof(hb_onehash_job);
+    J.block_off = offsetof(hb_onehash_job, block);
+    J.block_stride = sizeof(hb_onehash_job);
+    J.own_seeds = true;
+    J.seed_off = offsetof(hb_onehash_job, seed);
+    J.len_off = offsetof(hb_onehash_job, seed_len);
+    if (int rc = onehash_run(c, P, src, (flags & HB_DATA_ON_DEVICE) != 0, J, nullptr, nullptr)) return rc;
+    const uint8_t *out = (const uint8_t *)c->oh_out.p;
+    for (size_t j = 0; j < (size_t)njobs; ++j) memcpy(responses_out + order[j] * 32, out + j * 32, 32);
+    return 0;
+}
+
+uint64_t hb_onehash_device_min_jobs(void) { return OH_DEVICE_MIN_JOBS; }
 
 int hb_fill_random(hb_ctx *c, uint8_t *dev_ptr, uint64_t len, uint64_t seed) {
     if (!c) return HB_EINVAL;

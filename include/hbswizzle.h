@@ -301,6 +301,71 @@ typedef struct hb_merkle_leaf_desc {
 int hb_merkle_leaves_many(hb_ctx *ctx, const hb_merkle_leaf_desc *proofs, uint64_t nproofs,
                           uint32_t flags);
 
+/* OneHash challenges of many files in one call.
+ * Replaces heartbeat/OneHash/OneHash.py:92-110 (generate_challenges: its
+ * generate_seeds chain and its num meet_challenge calls) for nfiles files,
+ * each under its own secret, first seed, num and blocks (pick_blocks draws
+ * from Python's generator and stays with the caller).  With
+ * c = min(1024, len / 10), s_0 = s0 and s_{k+1} = SHA-256(s_k || secret):
+ *   seeds_out[job]     = s_k                                       (32 bytes)
+ *   responses_out[job] = SHA-256(part(blocks[k]) || s_k)           (32 bytes)
+ * for job = (the num of the files before) + k, where part(b) is
+ * data[b : b + c] when b <= len - c, and otherwise, with a = b - (len - c),
+ * data[b : min(b + a, len)] || data[0 : c - a]: the reference's first read
+ * stops at the end of the file, so the part is shorter than c when a > c / 2.
+ * Two launches serve the whole batch: the seed chains (a lane per file; on
+ * the host for a few files, and always for a secret of more than 87 bytes)
+ * and the responses (a lane per job).  A host file of more than
+ * max(2 * num * 1024, 8 MiB) bytes is not uploaded: only its jobs' segments
+ * go up.
+ * flags: HB_DATA_ON_DEVICE (every `data` is a device pointer), and at most
+ * one of HB_ONEHASH_CHAIN_HOST / HB_ONEHASH_CHAIN_DEVICE to force where the
+ * chains run; anything else returns HB_EINVAL.  Every descriptor is checked
+ * before the first launch: every block < len, no NULL buffer (secret may be
+ * NULL when secret_len == 0, data when len == 0, blocks when num == 0); more
+ * than 2^31 jobs in all is HB_EUNSUPPORTED.  nfiles = 0 is a no-op. */
+#define HB_ONEHASH_CHAIN_HOST 64u
+#define HB_ONEHASH_CHAIN_DEVICE 128u
+#define HB_ONEHASH_MAX_SEED_LEN 64u
+typedef struct hb_onehash_gen_desc {
+    const uint8_t *data;      /* host, or device with HB_DATA_ON_DEVICE; may be NULL when len == 0 */
+    uint64_t len;             /* the file's size */
+    const uint8_t *s0;        /* the first seed, 32 bytes: SHA-256 of the root seed */
+    const uint8_t *secret;    /* secret_len bytes of any length */
+    uint64_t secret_len;
+    uint64_t num;             /* challenges */
+    const uint64_t *blocks;   /* host, num positions, each < len */
+} hb_onehash_gen_desc;
+int hb_onehash_generate_many(hb_ctx *ctx, const hb_onehash_gen_desc *files, uint64_t nfiles,
+                             uint8_t *seeds_out, uint8_t *responses_out, uint32_t flags);
+
+/* OneHash responses of many challenges in one call (meet_challenge,
+ * OneHash.py:112-138).  Job j, over file jobs[j].file:
+ *   responses_out[j] = SHA-256(part(block) || seed[0 : seed_len])  (32 bytes)
+ * with part() as in hb_onehash_generate_many.  A lane per job; the jobs may
+ * name the files in any order, and a file is uploaded (or gathered) once
+ * however many jobs read it, by the same threshold with num = the file's
+ * jobs.  flags: HB_DATA_ON_DEVICE or 0.  Checked before the first launch:
+ * file < nfiles, block < the file's len, seed_len <= 64, no NULL buffer.
+ * njobs = 0 is a no-op. */
+typedef struct hb_onehash_file {
+    const uint8_t *data;      /* host, or device with HB_DATA_ON_DEVICE; may be NULL when len == 0 */
+    uint64_t len;
+} hb_onehash_file;
+typedef struct hb_onehash_job {
+    uint64_t file;            /* index into files */
+    uint64_t block;
+    uint64_t seed_len;        /* 0..64 */
+    uint8_t seed[64];
+} hb_onehash_job;
+int hb_onehash_meet_many(hb_ctx *ctx, const hb_onehash_file *files, uint64_t nfiles,
+                         const hb_onehash_job *jobs, uint64_t njobs, uint8_t *responses_out,
+                         uint32_t flags);
+
+/* Jobs from which heartbeat_amd.OneHash sends a call to the GPU (below, its
+ * host path is faster): the measured crossover, hb_onehash_host.hpp. */
+uint64_t hb_onehash_device_min_jobs(void);
+
 /* Swizzle encode of a run of blocks.
  * Replaces heartbeat/PySwizzle/PySwizzle.py:296-309 (the encode loop) and
  * cxx/shacham_waters_private.cxx:672-697.  For k in [0, nblocks):
