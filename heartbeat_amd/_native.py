@@ -28,6 +28,8 @@ HB_MERKLE_MAX_N = 65536
 HB_ONEHASH_CHAIN_HOST = 64
 HB_ONEHASH_CHAIN_DEVICE = 128
 HB_ONEHASH_MAX_SEED_LEN = 64
+HB_ONEHASH_MAX_KEY_WORDS = 1024
+HB_ONEHASH_STATE_WORDS = 625
 HB_BUILD_EXPERIMENT = 1
 HB_BUILD_TEST_SWITCHES = 2
 
@@ -123,6 +125,20 @@ class OneHashJob(ctypes.Structure):
                 ("seed", ctypes.c_uint8 * 64)]
 
 
+class OneHashDrawDesc(ctypes.Structure):
+    """hb_onehash_draw_desc (hbswizzle.h): one file of an hb_onehash_pick_blocks_many call."""
+    _fields_ = [("len", ctypes.c_uint64), ("key", ctypes.c_void_p), ("key_words", ctypes.c_uint64),
+                ("num", ctypes.c_uint64), ("blocks_out", ctypes.c_void_p), ("state_out", ctypes.c_void_p)]
+
+
+class OneHashDrawnDesc(ctypes.Structure):
+    """hb_onehash_drawn_desc (hbswizzle.h): one file of an hb_onehash_generate_drawn_many call."""
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64), ("s0", ctypes.c_char_p),
+                ("secret", ctypes.c_char_p), ("secret_len", ctypes.c_uint64), ("num", ctypes.c_uint64),
+                ("key", ctypes.c_void_p), ("key_words", ctypes.c_uint64),
+                ("blocks_out", ctypes.c_void_p), ("state_out", ctypes.c_void_p)]
+
+
 ONEHASH_JOB_DTYPE = [("file", "<u8"), ("block", "<u8"), ("seed_len", "<u8"), ("seed", "u1", (64,))]
 
 
@@ -206,6 +222,10 @@ SIGNATURES = [
     ("hb_onehash_meet_many", _c.c_int, [_P, _c.POINTER(OneHashFile), _c.c_uint64, _P, _c.c_uint64, _P,
                                         _c.c_uint32]),
     ("hb_onehash_device_min_jobs", _c.c_uint64, []),
+    ("hb_onehash_pick_blocks_many", _c.c_int, [_P, _c.POINTER(OneHashDrawDesc), _c.c_uint64, _c.c_uint32]),
+    ("hb_onehash_generate_drawn_many", _c.c_int, [_P, _c.POINTER(OneHashDrawnDesc), _c.c_uint64, _P, _P,
+                                                  _c.c_uint32]),
+    ("hb_onehash_draw_device_min_jobs", _c.c_uint64, []),
 ]
 
 

@@ -1,6 +1,7 @@
 // The OneHash scheme's kernels (heartbeat/OneHash/OneHash.py:141-168 the seed
-// chain, :112-138 the responses): the chains of a batch of files and the
-// responses of a batch of jobs, two launches in all.
+// chain, :112-138 the responses, :170-189 the positions): the chains of a
+// batch of files and the responses of a batch of jobs, two launches in all,
+// and the positions of a batch of files, a third.
 #include "hb_kernels.hpp"
 #include "hb_onehash_args.hpp"
 
@@ -70,6 +71,75 @@ __global__ __launch_bounds__(64) void hb_onehash_resp_kernel(OhRespArgs A) {
     u32 d[8];
     hb_oh_hash(F.data, F.len, P, A.seeds + job * A.seed_stride, seed_len, d);
     for (int t = 0; t < 8; ++t) A.resp[job * 8 + t] = hb_bswap(d[t]);
+}
+
+// ------------------------------------------------------------------ positions
+// A wave per file draws the file's positions (pick_blocks, hb_onehash_draw.hpp)
+// from one generator state in LDS (2,496 bytes).  Lane 0 seeds it -- a serial
+// recurrence.  Then, array by array: the 624 elements are regenerated 64 at a
+// time in index order, every chunk reading before it writes; the array's
+// attempts are tempered and tested 64 at a time, and the accepted values go
+// out in stream order by a ballot and a prefix count, up to the attempt that
+// yields the num-th.  The state that comes back is the array in use and the
+// words consumed in it: nothing is regenerated past the last attempt.
+// A workgroup is one wave, as for the responses: few files, latency-bound.
+__global__ __launch_bounds__(64) void hb_onehash_draw_kernel(OhDrawArgs A) {
+    __shared__ u32 mt[HB_MT_N];
+    const u64 f = blockIdx.x;
+    const u32 lane = threadIdx.x;
+    if (f >= A.nfiles) return;
+    const OhDraw D = A.draws[f];
+    if (lane == 0) hb_mt_seed(mt, A.keys + D.key0, D.key_words);
+    __syncthreads();
+    const u64 num = D.len ? D.num : 0;   // the host has refused len = 0 with num > 0: no attempt could be accepted
+    const u32 k = hb_mt_bits(D.len), w = hb_mt_words(k);
+    const u32 attempts = HB_MT_N / w;
+    u64 *out = A.blocks + D.job0;
+    u32 used = HB_MT_N;
+    u64 made = 0;
+    HB_NOUNROLL
+    while (made < num) {
+        HB_NOUNROLL
+        for (u32 base = 0; base < HB_MT_N; base += HB_MT_CHUNK) {
+            const u32 i = base + lane;
+            u32 v = 0;
+            if (i < HB_MT_N) v = hb_mt_next(mt, i);
+            __syncthreads();
+            if (i < HB_MT_N) mt[i] = v;
+            __syncthreads();
+        }
+        HB_NOUNROLL
+        for (u32 a0 = 0; a0 < attempts; a0 += HB_MT_CHUNK) {
+            const u32 a = a0 + lane;
+            u64 r = 0;
+            const bool ok = a < attempts && hb_mt_attempt(mt, a, D.len, k, r);
+            const u64 mask = __ballot(ok);
+            const u64 need = num - made;
+            const u32 before = (u32)__popcll(mask & ((1ull << lane) - 1ull));
+            const u32 total = (u32)__popcll(mask);
+            if (ok && before < need) out[made + before] = r;
+            if (total >= need) {
+                // the lane whose attempt yields the last value closes the stream
+                const u64 last = __ballot(ok && before + 1 == need);
+                used = (a0 + (u32)__ffsll((unsigned long long)last)) * w;
+                made = num;
+                break;
+            }
+            made += total;
+            used = (a0 + HB_MT_CHUNK < attempts ? a0 + HB_MT_CHUNK : attempts) * w;
+        }
+    }
+    if (A.states) {
+        __syncthreads();
+        u32 *st = A.states + f * HB_MT_STATE_WORDS;
+        for (u32 i = lane; i < HB_MT_N; i += HB_MT_CHUNK) st[i] = mt[i];
+        if (lane == 0) st[HB_MT_N] = used;
+    }
+}
+
+hipError_t hb_launch_onehash_draw(const OhDrawArgs &A, hipStream_t s) {
+    hipLaunchKernelGGL(hb_onehash_draw_kernel, dim3((u32)A.nfiles), dim3(64), 0, s, A);
+    return hipGetLastError();
 }
 
 hipError_t hb_launch_onehash_chain(const OhChainArgs &A, hipStream_t s) {

@@ -2,6 +2,7 @@
 // device table (hb_kern_onehash.hip, hb_runtime.cpp, hb_onehash_host.hpp).
 #pragma once
 #include "hb_onehash.hpp"
+#include "hb_onehash_draw.hpp"
 
 // OhFile::flags
 #define HB_OH_GATHER 1u       // a host file too large to upload: data holds its jobs' segments
@@ -41,4 +42,21 @@ struct OhRespArgs {
     u64 len_stride;
     u32 *resp;                        // [jobs] x 32 bytes
     unsigned int *flags;              // bit 2: a segment outside its buffer, or a seed too long
+};
+
+// One file of hb_onehash_draw_kernel: num positions in [0, len) from the
+// generator seeded with keys[key0 : key0 + key_words].
+struct OhDraw {
+    u64 len;
+    u64 key0, key_words;         // the file's key in the batch's key array
+    u64 job0, num;               // its positions at blocks[job0 : job0 + num]
+};
+
+// hb_onehash_draw_kernel: a wave per file.
+struct OhDrawArgs {
+    const OhDraw *draws;
+    u64 nfiles;
+    const u32 *keys;
+    u64 *blocks;                 // [jobs]
+    u32 *states;                 // [nfiles] x HB_MT_STATE_WORDS, or NULL
 };

@@ -1,7 +1,8 @@
-// hb_onehash_host.hpp -- host side of hb_onehash_generate_many and
-// hb_onehash_meet_many (pure C++, no HIP calls): the descriptor checks, the
-// per-file table the kernels index, the host seed chain, which host files are
-// uploaded whole and which are gathered, and the gather itself.
+// hb_onehash_host.hpp -- host side of hb_onehash_generate_many,
+// hb_onehash_meet_many, hb_onehash_pick_blocks_many and
+// hb_onehash_generate_drawn_many (pure C++, no HIP calls): the descriptor
+// checks, the per-file tables the kernels index, the host seed chain, which
+// host files are uploaded whole and which are gathered, and the gather itself.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -41,6 +42,24 @@ const uint64_t OH_DEVICE_MIN_JOBS = 256;
 // the host's fastest.
 const uint64_t OH_CHAIN_DEVICE_MIN_FILES = 20;
 
+// Jobs from which a GPU generate call of one file draws its positions on the
+// device when the caller does not say (hb_onehash_draw_device_min_jobs).
+// generate_challenges on one 1 MiB file, GPU path forced, the parent commit's
+// tree (pick_blocks in Python) against this one with draw="device", min .. max
+// ms of 5 alternating rounds (profiles/many/onehash_draw_rate.json, "sweep"):
+//   jobs   parent, disk    device draw, disk   parent, resident   device draw, resident
+//    256   0.434..0.526    0.488..0.505        0.318..0.328       0.424..0.434
+//    512   0.579..0.612    0.598..0.695        0.479..0.509       0.529..0.540
+//   1024   0.945..0.962    0.830..0.840        0.845..0.861       0.760..0.775
+//   4096   3.051..3.394    2.133..2.295        2.957..3.009       1.996..2.098
+// The draw launch costs 0.1 ms a call (one lane seeds the state) and saves
+// 0.25 us a job: 1024 is the first measured count at which the device draw's
+// slowest round beats the parent's fastest, from disk and resident.  Calls of
+// several files stay opt-in: 256 files x 1000 measured 196..242 against
+// 238..272 ms from disk and 159..221 against 195..263 resident, lower at both
+// ends but with the slowest round above the parent's fastest.
+const uint64_t OH_DRAW_DEVICE_MIN_JOBS = 1024;
+
 // A host file is uploaded whole up to this many bytes, the Merkle scheme's
 // threshold; above it only the jobs' segments go to the device.
 inline uint64_t oh_upload_max(uint64_t jobs) {
@@ -67,10 +86,13 @@ inline void oh_bytes(const u32 w[8], uint8_t *b) {
 
 inline bool oh_block_ok(uint64_t block, uint64_t len) { return block < len; }
 
-// hb_onehash_generate_many: check every descriptor and fill the table (data
-// pointers are the runtime's).  code / err as the C ABI reports them.
-inline bool oh_plan_generate(const hb_onehash_gen_desc *d, uint64_t nfiles, const uint8_t *seeds_out,
-                             const uint8_t *responses_out, OhPlan &P, int &code, std::string &err) {
+// The generate side's descriptors, hb_onehash_gen_desc or
+// hb_onehash_drawn_desc: check every one and fill the table (data pointers
+// are the runtime's).  positions(i, who, code, err) checks where file i's
+// blocks come from.  code / err as the C ABI reports them.
+template <class Desc, class Positions>
+inline bool oh_plan_files(const Desc *d, uint64_t nfiles, const uint8_t *seeds_out, const uint8_t *responses_out,
+                          OhPlan &P, int &code, std::string &err, Positions positions) {
     P.files.assign((size_t)nfiles, OhFile());
     P.jobs = 0;
     code = HB_EINVAL;
@@ -83,16 +105,11 @@ inline bool oh_plan_generate(const hb_onehash_gen_desc *d, uint64_t nfiles, cons
             err = "more than 2^31 OneHash jobs in one call";
             return false;
         }
-        if (!d[i].s0 || (!d[i].secret && d[i].secret_len) || (!d[i].data && d[i].len) ||
-            (!d[i].blocks && d[i].num)) {
+        if (!d[i].s0 || (!d[i].secret && d[i].secret_len) || (!d[i].data && d[i].len)) {
             err = who + "NULL buffer";
             return false;
         }
-        for (uint64_t k = 0; k < d[i].num; ++k)
-            if (!oh_block_ok(d[i].blocks[k], d[i].len)) {
-                err = who + "block " + std::to_string(d[i].blocks[k]) + " outside the file";
-                return false;
-            }
+        if (!positions(i, who, code, err)) return false;
         F.len = F.file_size = d[i].len;
         F.job0 = P.jobs;
         F.n = (u32)d[i].num;
@@ -104,6 +121,119 @@ inline bool oh_plan_generate(const hb_onehash_gen_desc *d, uint64_t nfiles, cons
         err = "NULL buffer";
         return false;
     }
+    code = 0;
+    return true;
+}
+
+// hb_onehash_generate_many: the caller's blocks, each inside its file.
+inline bool oh_plan_generate(const hb_onehash_gen_desc *d, uint64_t nfiles, const uint8_t *seeds_out,
+                             const uint8_t *responses_out, OhPlan &P, int &code, std::string &err) {
+    return oh_plan_files(d, nfiles, seeds_out, responses_out, P, code, err,
+                         [d](uint64_t i, const std::string &who, int &, std::string &e) {
+                             if (!d[i].blocks && d[i].num) {
+                                 e = who + "NULL buffer";
+                                 return false;
+                             }
+                             for (uint64_t k = 0; k < d[i].num; ++k)
+                                 if (!oh_block_ok(d[i].blocks[k], d[i].len)) {
+                                     e = who + "block " + std::to_string(d[i].blocks[k]) + " outside the file";
+                                     return false;
+                                 }
+                             return true;
+                         });
+}
+
+// The draws of a batch: the kernel's table and the files' keys, end to end.
+struct OhDrawPlan {
+    std::vector<OhDraw> draws;
+    std::vector<u32> keys;
+    uint64_t jobs = 0;
+    bool states = false;   // a file asks for its final state
+};
+
+// One file's draw (len, key, num, blocks_out) as both entry points check it.
+inline bool oh_draw_ok(uint64_t len, const uint32_t *key, uint64_t key_words, uint64_t num,
+                       const uint64_t *blocks_out, const std::string &who, int &code, std::string &err) {
+    if (key_words > HB_ONEHASH_MAX_KEY_WORDS) {
+        code = HB_EUNSUPPORTED;
+        err = who + "a key of more than " + std::to_string(HB_ONEHASH_MAX_KEY_WORDS) + " words";
+        return false;
+    }
+    code = HB_EINVAL;
+    if (len == 0 && num) {
+        err = who + "no position in an empty range";
+        return false;
+    }
+    if (key_words == 0) {
+        err = who + "an empty key";
+        return false;
+    }
+    if (!key || (!blocks_out && num)) {
+        err = who + "NULL buffer";
+        return false;
+    }
+    return true;
+}
+
+inline void oh_draw_add(OhDrawPlan &D, uint64_t len, const uint32_t *key, uint64_t key_words, uint64_t num,
+                        const uint32_t *state_out) {
+    OhDraw W;
+    W.len = len;
+    W.key0 = D.keys.size();
+    W.key_words = key_words;
+    W.job0 = D.jobs;
+    W.num = num;
+    D.draws.push_back(W);
+    D.keys.insert(D.keys.end(), key, key + key_words);
+    D.jobs += num;
+    D.states |= state_out != nullptr;
+}
+
+// hb_onehash_pick_blocks_many: check every descriptor, then fill the table.
+inline bool oh_plan_draw(const hb_onehash_draw_desc *d, uint64_t nfiles, OhDrawPlan &D, int &code,
+                         std::string &err) {
+    D = OhDrawPlan();
+    uint64_t jobs = 0;
+    if (nfiles >> 31) {
+        code = HB_EUNSUPPORTED;
+        err = "more than 2^31 OneHash jobs in one call";
+        return false;
+    }
+    for (uint64_t i = 0; i < nfiles; ++i) {
+        if (d[i].num > (1ull << 31) || jobs + d[i].num > (1ull << 31)) {
+            code = HB_EUNSUPPORTED;
+            err = "more than 2^31 OneHash jobs in one call";
+            return false;
+        }
+        jobs += d[i].num;
+        if (!oh_draw_ok(d[i].len, d[i].key, d[i].key_words, d[i].num, d[i].blocks_out,
+                        "file " + std::to_string(i) + ": ", code, err))
+            return false;
+    }
+    for (uint64_t i = 0; i < nfiles; ++i)
+        oh_draw_add(D, d[i].len, d[i].key, d[i].key_words, d[i].num, d[i].state_out);
+    code = 0;
+    return true;
+}
+
+// hb_onehash_generate_drawn_many: hb_onehash_generate_many's checks with the
+// draw's in the place of the blocks', and both tables.
+inline bool oh_plan_generate_drawn(const hb_onehash_drawn_desc *d, uint64_t nfiles, const uint8_t *seeds_out,
+                                   const uint8_t *responses_out, OhPlan &P, OhDrawPlan &D, int &code,
+                                   std::string &err) {
+    D = OhDrawPlan();
+    if (nfiles >> 31) {
+        code = HB_EUNSUPPORTED;
+        err = "more than 2^31 OneHash jobs in one call";
+        return false;
+    }
+    if (!oh_plan_files(d, nfiles, seeds_out, responses_out, P, code, err,
+                       [d](uint64_t i, const std::string &who, int &c, std::string &e) {
+                           return oh_draw_ok(d[i].len, d[i].key, d[i].key_words, d[i].num, d[i].blocks_out, who, c, e);
+                       }))
+        return false;
+    for (uint64_t i = 0; i < nfiles; ++i)
+        oh_draw_add(D, d[i].len, d[i].key, d[i].key_words, d[i].num, d[i].state_out);
     code = 0;
     return true;
 }

@@ -101,6 +101,7 @@ hipError_t hb_launch_merkle_tree(const MkTreeArgs &, u64, hipStream_t);
 // hb_kern_onehash.hip
 hipError_t hb_launch_onehash_chain(const OhChainArgs &, hipStream_t);
 hipError_t hb_launch_onehash_resp(const OhRespArgs &, hipStream_t);
+hipError_t hb_launch_onehash_draw(const OhDrawArgs &, hipStream_t);
 
 namespace {
 
@@ -197,6 +198,11 @@ struct hb_ctx {
     // host files and the gathered segments; their pinned staging (results)
     DevBuf oh_files, oh_jobs, oh_seeds, oh_resp, oh_data, oh_gather;
     HostBuf oh_out;
+    // hb_onehash_pick_blocks_many / hb_onehash_generate_drawn_many: the draw
+    // table and keys, the final generator states (the positions are oh_jobs);
+    // their pinned staging (positions | states)
+    DevBuf oh_draw, oh_states;
+    HostBuf oh_dout;
     HostBuf hscratch;    // pinned staging of the encode's small host round trips (alpha, MFMA tables)
     // the alpha D2H into hscratch done / the MFMA-table H2D out of it done
     // (not yet waited for: the next round trip must wait before reusing hscratch)
@@ -3973,7 +3979,7 @@ void hb_ctx_destroy(hb_ctx *c) {
                       &c->pr_jobs, &c->pr_pass, &c->pr_q, &c->pr_win, &c->pr_surv, &c->pr_cnt,
                       &c->mk_files, &c->mk_seeds, &c->mk_offs, &c->mk_blobs, &c->mk_nodes, &c->mk_data,
                       &c->mk_gather, &c->oh_files, &c->oh_jobs, &c->oh_seeds, &c->oh_resp, &c->oh_data,
-                      &c->oh_gather};
+                      &c->oh_gather, &c->oh_draw, &c->oh_states};
     for (DevBuf *b : bufs) b->release();
     if (c->hres) (void)hipHostFree(c->hres);
     c->gstage[0].release();
@@ -3982,6 +3988,7 @@ void hb_ctx_destroy(hb_ctx *c) {
     c->bhost.release();
     c->mk_out.release();
     c->oh_out.release();
+    c->oh_dout.release();
     if (c->t0) (void)hipFree(c->t0);
     if (c->queue) (void)hipFree(c->queue);
     if (c->k0) (void)hipEventDestroy(c->k0);
@@ -5269,20 +5276,72 @@ struct OhJobs {
     u64 seed_off, len_off;
 };
 
+const size_t OH_STATE_BYTES = HB_MT_STATE_WORDS * 4;
+
+// The draw launch of a planned batch: the positions into c->oh_jobs, the
+// final states into c->oh_states.  Not synchronised.
+int onehash_draw_launch(hb_ctx *c, const OhDrawPlan &D) {
+    const size_t nfiles = D.draws.size();
+    const size_t tab = nfiles * sizeof(OhDraw), keys = D.keys.size() * 4;
+    HB_CHECK(c->oh_draw.ensure(tab + keys), "hipMalloc");
+    HB_CHECK(c->oh_jobs.ensure((size_t)D.jobs * 8), "hipMalloc");
+    if (D.states) HB_CHECK(c->oh_states.ensure(nfiles * OH_STATE_BYTES), "hipMalloc");
+    HB_CHECK(c->oh_dout.ensure((size_t)D.jobs * 8 + (D.states ? nfiles * OH_STATE_BYTES : 0)), "hipHostMalloc");
+    HB_CHECK(hipMemcpyAsync(c->oh_draw.p, D.draws.data(), tab, hipMemcpyHostToDevice, c->stream), "H2D");
+    HB_CHECK(hipMemcpyAsync((uint8_t *)c->oh_draw.p + tab, D.keys.data(), keys, hipMemcpyHostToDevice, c->stream),
+             "H2D");
+    OhDrawArgs A;
+    A.draws = (const OhDraw *)c->oh_draw.p;
+    A.nfiles = nfiles;
+    A.keys = (const u32 *)((const uint8_t *)c->oh_draw.p + tab);
+    A.blocks = (u64 *)c->oh_jobs.p;
+    A.states = D.states ? (u32 *)c->oh_states.p : nullptr;
+    HB_CHECK(hb_launch_onehash_draw(A, c->stream), "hb_onehash_draw_kernel launch");
+    return 0;
+}
+
+// The positions and states of a launched draw on their way to c->oh_dout
+// (positions | states).  Not synchronised.
+int onehash_draw_fetch(hb_ctx *c, const OhDrawPlan &D) {
+    uint8_t *out = (uint8_t *)c->oh_dout.p;
+    if (D.jobs)
+        HB_CHECK(hipMemcpyAsync(out, c->oh_jobs.p, (size_t)D.jobs * 8, hipMemcpyDeviceToHost, c->stream), "D2H");
+    if (D.states)
+        HB_CHECK(hipMemcpyAsync(out + (size_t)D.jobs * 8, c->oh_states.p, D.draws.size() * OH_STATE_BYTES,
+                                hipMemcpyDeviceToHost, c->stream), "D2H");
+    return 0;
+}
+
+// c->oh_dout, synchronised, into the callers' buffers (Desc: blocks_out, state_out).
+extern "C++" {
+template <class Desc>
+void onehash_draw_scatter(hb_ctx *c, const OhDrawPlan &D, const Desc *files) {
+    const uint8_t *out = (const uint8_t *)c->oh_dout.p;
+    for (size_t i = 0; i < D.draws.size(); ++i) {
+        if (D.draws[i].num) memcpy(files[i].blocks_out, out + (size_t)D.draws[i].job0 * 8, (size_t)D.draws[i].num * 8);
+        if (files[i].state_out) memcpy(files[i].state_out, out + (size_t)D.jobs * 8 + i * OH_STATE_BYTES, OH_STATE_BYTES);
+    }
+}
+}
+
 // The launches of a planned batch.  P.files is complete but for the data
 // pointers.  Generate side: host_seeds (jobs x 32 bytes) when the host walked
 // every chain, else the device chain fills the seeds, after the slices of
-// files with HB_OH_HOST_CHAIN came up from host_long.  Leaves c->oh_out
-// holding responses | seeds (the generate side), synchronised.
+// files with HB_OH_HOST_CHAIN came up from host_long.  With `draw` the
+// positions are not J.rec's: the draw kernel leaves them in c->oh_jobs, and
+// those of gathered files come down before the gather.  Leaves c->oh_out
+// holding responses | seeds (the generate side) and c->oh_dout the draw's
+// positions | states, synchronised.
 int onehash_run(hb_ctx *c, OhPlan &P, const std::vector<OhSrc> &src, bool data_dev, const OhJobs &J,
-                const uint8_t *host_seeds, const uint8_t *host_long) {
+                const uint8_t *host_seeds, const uint8_t *host_long, const OhDrawPlan *draw = nullptr) {
     const size_t nfiles = P.files.size();
     const size_t jobs = (size_t)P.jobs;
     HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
     if (int rc = ensure_ctl(c, 1)) return rc;
+    const uint8_t *rec = J.rec;
     auto block_of = [&](u64 j) {
         u64 b;
-        memcpy(&b, J.rec + J.block_off + j * J.block_stride, 8);
+        memcpy(&b, rec + J.block_off + j * J.block_stride, 8);
         return b;
     };
     // where every file's bytes are
@@ -5310,6 +5369,20 @@ int onehash_run(hb_ctx *c, OhPlan &P, const std::vector<OhSrc> &src, bool data_d
     HB_CHECK(c->oh_data.ensure(up_bytes), "hipMalloc");
     HB_CHECK(c->oh_gather.ensure(g_bytes), "hipMalloc");
     HB_CHECK(c->oh_out.ensure(jobs * 64), "hipHostMalloc");
+    if (draw) {
+        if (int rc = onehash_draw_launch(c, *draw)) return rc;
+        rec = (const uint8_t *)c->oh_dout.p;
+        if (g_bytes) {
+            for (size_t i = 0; i < nfiles; ++i) {
+                const OhFile &F = P.files[i];
+                if (F.flags & HB_OH_GATHER)
+                    HB_CHECK(hipMemcpyAsync((uint8_t *)c->oh_dout.p + (size_t)F.job0 * 8,
+                                            (const uint8_t *)c->oh_jobs.p + (size_t)F.job0 * 8, (size_t)F.n * 8,
+                                            hipMemcpyDeviceToHost, c->stream), "D2H");
+            }
+            HB_CHECK(hipStreamSynchronize(c->stream), "hb_onehash_draw_kernel");
+        }
+    }
     std::vector<uint8_t> stage(g_bytes);   // the gathered segments: alive until the synchronise
     if (!data_dev)
         for (size_t i = 0; i < nfiles; ++i) {
@@ -5332,7 +5405,7 @@ int onehash_run(hb_ctx *c, OhPlan &P, const std::vector<OhSrc> &src, bool data_d
     if (g_bytes) HB_CHECK(hipMemcpyAsync(c->oh_gather.p, stage.data(), g_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
     HB_CHECK(hipMemcpyAsync(c->oh_files.p, P.files.data(), nfiles * sizeof(OhFile), hipMemcpyHostToDevice,
                             c->stream), "H2D");
-    HB_CHECK(hipMemcpyAsync(c->oh_jobs.p, J.rec, J.rec_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
+    if (!draw) HB_CHECK(hipMemcpyAsync(c->oh_jobs.p, J.rec, J.rec_bytes, hipMemcpyHostToDevice, c->stream), "H2D");
     unsigned int *flw = flags_word(c);
     HB_CHECK(hipMemsetAsync(flw, 0, 4, c->stream), "hipMemsetAsync");
     HB_CHECK(hipEventRecord(c->k0, c->stream), "hipEventRecord");
@@ -5373,6 +5446,8 @@ int onehash_run(hb_ctx *c, OhPlan &P, const std::vector<OhSrc> &src, bool data_d
     HB_CHECK(hipMemcpyAsync(out, c->oh_resp.p, jobs * 32, hipMemcpyDeviceToHost, c->stream), "D2H");
     if (!J.own_seeds)
         HB_CHECK(hipMemcpyAsync(out + jobs * 32, c->oh_seeds.p, jobs * 32, hipMemcpyDeviceToHost, c->stream), "D2H");
+    if (draw)
+        if (int rc = onehash_draw_fetch(c, *draw)) return rc;
     HB_CHECK(hipEventRecord(c->k1, c->stream), "hipEventRecord");
     u32 fl = 0;
     HB_CHECK(hipMemcpyAsync(&fl, flw, 4, hipMemcpyDeviceToHost, c->stream), "D2H");
@@ -5463,6 +5538,81 @@ int hb_onehash_meet_many(hb_ctx *c, const hb_onehash_file *files, uint64_t nfile
 }
 
 uint64_t hb_onehash_device_min_jobs(void) { return OH_DEVICE_MIN_JOBS; }
+
+int hb_onehash_pick_blocks_many(hb_ctx *c, const hb_onehash_draw_desc *files, uint64_t nfiles, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    if (flags) return fail(c, HB_EINVAL, "hb_onehash_pick_blocks_many: unsupported flags");
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "NULL buffer");
+    c->ph_valid = false;
+    OhDrawPlan D;
+    int code = 0;
+    std::string err;
+    if (!oh_plan_draw(files, nfiles, D, code, err)) return fail(c, code, err);
+    if (D.jobs == 0 && !D.states) return 0;
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    if (int rc = onehash_draw_launch(c, D)) return rc;
+    if (int rc = onehash_draw_fetch(c, D)) return rc;
+    HB_CHECK(hipStreamSynchronize(c->stream), "hb_onehash_draw_kernel");
+    onehash_draw_scatter(c, D, files);
+    return 0;
+}
+
+int hb_onehash_generate_drawn_many(hb_ctx *c, const hb_onehash_drawn_desc *files, uint64_t nfiles,
+                                   uint8_t *seeds_out, uint8_t *responses_out, uint32_t flags) {
+    if (!c) return HB_EINVAL;
+    settle(c);
+    const u32 chain = flags & (HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE);
+    if ((flags & ~(HB_DATA_ON_DEVICE | HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE)) ||
+        chain == (HB_ONEHASH_CHAIN_HOST | HB_ONEHASH_CHAIN_DEVICE))
+        return fail(c, HB_EINVAL, "hb_onehash_generate_drawn_many: unsupported flags");
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "NULL buffer");
+    c->ph_valid = false;
+    OhPlan P;
+    OhDrawPlan D;
+    int code = 0;
+    std::string err;
+    if (!oh_plan_generate_drawn(files, nfiles, seeds_out, responses_out, P, D, code, err)) return fail(c, code, err);
+    if (P.jobs == 0) {
+        // no challenge: the seeded states, if a file asks for its
+        if (!D.states) return 0;
+        HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+        if (int rc = onehash_draw_launch(c, D)) return rc;
+        if (int rc = onehash_draw_fetch(c, D)) return rc;
+        HB_CHECK(hipStreamSynchronize(c->stream), "hb_onehash_draw_kernel");
+        onehash_draw_scatter(c, D, files);
+        return 0;
+    }
+    const size_t jobs = (size_t)P.jobs;
+    std::vector<OhSrc> src((size_t)nfiles);
+    for (size_t i = 0; i < (size_t)nfiles; ++i) src[i] = {files[i].data, files[i].len};
+    const bool host_chain = chain ? chain == HB_ONEHASH_CHAIN_HOST : nfiles < OH_CHAIN_DEVICE_MIN_FILES;
+    std::vector<uint8_t> seeds;
+    bool any_long = false;
+    for (const OhFile &F : P.files) any_long |= (F.flags & HB_OH_HOST_CHAIN) && F.n;
+    if (host_chain || any_long) {
+        seeds.resize(jobs * 32);
+        for (size_t i = 0; i < (size_t)nfiles; ++i)
+            if (host_chain || (P.files[i].flags & HB_OH_HOST_CHAIN))
+                oh_host_chain(P.files[i], files[i].secret, files[i].secret_len, seeds.data() + (size_t)P.files[i].job0 * 32);
+    }
+    OhJobs J;
+    memset(&J, 0, sizeof J);
+    J.rec_bytes = jobs * 8;   // the draw's positions, in place of an upload
+    J.block_stride = 8;
+    if (int rc = onehash_run(c, P, src, (flags & HB_DATA_ON_DEVICE) != 0, J, host_chain ? seeds.data() : nullptr,
+                             seeds.data(), &D))
+        return rc;
+    const uint8_t *out = (const uint8_t *)c->oh_out.p;
+    memcpy(responses_out, out, jobs * 32);
+    memcpy(seeds_out, out + jobs * 32, jobs * 32);
+    onehash_draw_scatter(c, D, files);
+    return 0;
+}
+
+uint64_t hb_onehash_draw_device_min_jobs(void) { return OH_DRAW_DEVICE_MIN_JOBS; }
 
 int hb_fill_random(hb_ctx *c, uint8_t *dev_ptr, uint64_t len, uint64_t seed) {
     if (!c) return HB_EINVAL;

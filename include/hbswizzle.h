@@ -366,6 +366,63 @@ int hb_onehash_meet_many(hb_ctx *ctx, const hb_onehash_file *files, uint64_t nfi
  * host path is faster): the measured crossover, hb_onehash_host.hpp. */
 uint64_t hb_onehash_device_min_jobs(void);
 
+/* The positions of OneHash.pick_blocks for many files in one launch
+ * (OneHash.py:170-189): file i's num draws of randint(0, len - 1) from
+ * Python's generator after random.seed(root_seed), bit for bit (CPython's
+ * MT19937, seed version 2).  The caller makes the key from the root seed: for
+ * str (UTF-8), bytes and bytearray n = int.from_bytes(a + sha512(a).digest(),
+ * "big"), for int n = abs(a); key = the 32-bit words of n, least significant
+ * first, [0] for n = 0.  The device never sees the root seed.
+ *   blocks_out[k] = the k-th position                         (num values)
+ *   state_out     = what random.getstate() holds afterwards: mt[0..623] and
+ *                   the index (the twist is lazy: 624 after exactly 624 * m
+ *                   words)                                     (625 words)
+ * A wave per file.  flags: 0.  Every descriptor is checked before the launch
+ * and nothing is written when one fails (hb_last_error names the file):
+ * len == 0 with num > 0, key_words == 0, a NULL key, and a NULL blocks_out
+ * with num > 0 are HB_EINVAL; key_words above HB_ONEHASH_MAX_KEY_WORDS and
+ * more than 2^31 jobs in all are HB_EUNSUPPORTED.  nfiles = 0 is a no-op. */
+#define HB_ONEHASH_MAX_KEY_WORDS 1024u      /* seeds of up to 4032 bytes */
+typedef struct hb_onehash_draw_desc {
+    uint64_t len;            /* positions are drawn in [0, len); >= 1 when num > 0 */
+    const uint32_t *key;     /* key_words words, least significant first */
+    uint64_t key_words;      /* 1 .. HB_ONEHASH_MAX_KEY_WORDS */
+    uint64_t num;
+    uint64_t *blocks_out;    /* host, num values; may be NULL when num == 0 */
+    uint32_t *state_out;     /* host, 625 words: mt[0..623], index; or NULL */
+} hb_onehash_draw_desc;
+int hb_onehash_pick_blocks_many(hb_ctx *ctx, const hb_onehash_draw_desc *files,
+                                uint64_t nfiles, uint32_t flags);
+
+/* hb_onehash_generate_many with the positions drawn on the device: file i's
+ * blocks are those of hb_onehash_pick_blocks_many for (len, key, num).  One
+ * draw launch, then the chain and response launches; the positions stay in
+ * device memory between them and come back with the seeds and responses.
+ * For a host file above the upload threshold, whose segments the host
+ * gathers, the positions come down before the gather.  flags and checks are
+ * those of hb_onehash_generate_many (without its block check) and of
+ * hb_onehash_pick_blocks_many. */
+typedef struct hb_onehash_drawn_desc {
+    const uint8_t *data;      /* host, or device with HB_DATA_ON_DEVICE; may be NULL when len == 0 */
+    uint64_t len;             /* the file's size: positions are drawn in [0, len) */
+    const uint8_t *s0;        /* the first seed, 32 bytes: SHA-256 of the root seed */
+    const uint8_t *secret;    /* secret_len bytes of any length */
+    uint64_t secret_len;
+    uint64_t num;             /* challenges */
+    const uint32_t *key;      /* key_words words, least significant first */
+    uint64_t key_words;       /* 1 .. HB_ONEHASH_MAX_KEY_WORDS */
+    uint64_t *blocks_out;     /* host, num values; may be NULL when num == 0 */
+    uint32_t *state_out;      /* host, 625 words, or NULL */
+} hb_onehash_drawn_desc;
+int hb_onehash_generate_drawn_many(hb_ctx *ctx, const hb_onehash_drawn_desc *files, uint64_t nfiles,
+                                   uint8_t *seeds_out, uint8_t *responses_out, uint32_t flags);
+
+/* Jobs from which heartbeat_amd.OneHash draws the positions of a GPU call of
+ * one file on the device when the caller does not say: the measured
+ * crossover, hb_onehash_host.hpp.  Calls of several files draw on the device
+ * only when asked to.  0: every call only when asked to. */
+uint64_t hb_onehash_draw_device_min_jobs(void);
+
 /* Swizzle encode of a run of blocks.
  * Replaces heartbeat/PySwizzle/PySwizzle.py:296-309 (the encode loop) and
  * cxx/shacham_waters_private.cxx:672-697.  For k in [0, nblocks):
