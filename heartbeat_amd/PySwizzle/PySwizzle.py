@@ -15,12 +15,15 @@ Same class names, constructor arguments, method signatures, defaults,
         prove(file, chal, tag) -> Proof           PySwizzle.py:333-370
         verify(proof, chal, state) -> bool        PySwizzle.py:372-395
         verify_many(items) -> [bool]              a loop over :372-395, one GPU call
+        encode_blocks / update / update_file / update_many, patch_tag (static)
+                                                  the body of :296-309 for listed blocks only
         prove_mixed(items) / verify_mixed(items)  (static) the same for any mix of beats
 
 Tags produced by encode keep their fixed-width big-endian image (``Tag.raw``)
 so prove can hand them to the GPU without converting 2^27 Python ints; the
 ``sigma`` list is materialised on first access.
 """
+import copy
 import ctypes
 import hashlib
 import hmac as _hmac
@@ -337,6 +340,228 @@ class PySwizzle(object):
             state.chunks = nblocks
             state.encrypt(beat.key)
             out.append((tag, state))
+        return out
+
+    # -- re-tagging listed blocks after an edit or an append
+    def _sorted_blocks(self, blocks):
+        """[(index, bytes)] in ascending order of index; every index once and
+        inside [0, 2^64)."""
+        out, seen = [], set()
+        for index, data in blocks:
+            i = int(index)
+            if i < 0 or i >> 64:
+                raise HeartbeatError("block index %d is outside [0, 2^64)" % i)
+            if i in seen:
+                raise HeartbeatError("block index %d is listed twice" % i)
+            seen.add(i)
+            out.append((i, bytes(data)))
+        out.sort(key=lambda t: t[0])
+        return out
+
+    def _open_state(self, state):
+        """A decrypted copy of `state` (its signature checked); the argument
+        is left as it was."""
+        st = copy.copy(state)
+        st.decrypt(self.key)
+        return st
+
+    def _pack_blocks(self, blocks):
+        """(indices, packed bytes) of ascending blocks for one descriptor of
+        hb_encode_blocks_many: all blocks whole but possibly the last."""
+        C = int(self.sectors) * self.sectorsize
+        for k, (i, data) in enumerate(blocks):
+            if len(data) > C or (len(data) < C and k + 1 < len(blocks)):
+                raise HeartbeatError("block %d has %d bytes, not %d" % (i, len(data), C))
+        return [i for i, _ in blocks], b"".join(d for _, d in blocks)
+
+    def encode_blocks(self, state, blocks):
+        """New tag values of listed blocks under the state's keys: `blocks` is
+        an iterable of (index, bytes).  Returns (indices, Tag): the indices in
+        ascending order and a Tag holding tag_i = F(i) + sum_j alpha_j m_ij mod
+        p (PySwizzle.py:296-309) of each, in that order -- the patch an owner
+        sends to the server (patch_tag).  Every block must be whole (sectors x
+        sectorsize bytes) except the one of the highest index, which may be
+        short.  The state's signature is checked and a copy is decrypted; the
+        argument is left as it was."""
+        self._check()
+        st = self._open_state(state)
+        blocks = self._sorted_blocks(blocks)
+        indices, data = self._pack_blocks(blocks)
+        p = int(self.prime)
+        raw = encode_blocks_many(p, int(self.sectors), [(st.f_key, st.alpha_key, indices, data)])[0]
+        return indices, Tag._from_raw(memoryview(raw), _native.width_of(p))
+
+    @staticmethod
+    def patch_tag(tag, indices, values, nblocks=None):
+        """A new Tag of `nblocks` values (default len(tag)): those of `tag`
+        with values[k] in place of block indices[k].  No key is needed: this is
+        the server's side of an update.  `values` is a Tag or a sequence of
+        ints.  A longer result must have every added index listed; a shorter
+        one drops the rest.  A tag that holds its fixed-width image keeps one;
+        a tag built from a list (fromdict) stays a list."""
+        n_old = len(tag)
+        n_new = n_old if nblocks is None else int(nblocks)
+        indices = [int(i) for i in indices]
+        if len(indices) != len(values):
+            raise HeartbeatError("%d indices for %d values" % (len(indices), len(values)))
+        for i in indices:
+            if i < 0 or i >= n_new:
+                raise HeartbeatError("block index %d is outside the tag's %d blocks" % (i, n_new))
+        listed = set(indices)
+        for i in range(n_old, n_new):
+            if i not in listed:
+                raise HeartbeatError("block %d is added but not listed" % i)
+        if tag._sigma is None:
+            w = tag._width
+            if isinstance(values, Tag) and values._sigma is None and values._width == w:
+                vraw = bytes(values._raw)
+            else:
+                vals = values.sigma if isinstance(values, Tag) else list(values)
+                try:
+                    vraw = b"".join(int(v).to_bytes(w, "big") for v in vals)
+                except OverflowError:
+                    raise HeartbeatError("a tag value does not fit the tag's %d bytes" % w)
+            # one copy of the image: the kept values, then the listed ones over it
+            keep = min(n_old, n_new) * w
+            img = np.zeros(n_new * w, dtype=np.uint8)
+            img[:keep] = np.frombuffer(tag._raw, dtype=np.uint8)[:keep]
+            vals = np.frombuffer(vraw, dtype=np.uint8).reshape(len(indices), w) if indices else None
+            rows = img.reshape(n_new, w)
+            for k, i in enumerate(indices):
+                rows[i] = vals[k]
+            return Tag._from_raw(memoryview(img), w)
+        vals = values.sigma if isinstance(values, Tag) else list(values)
+        sigma = list(tag.sigma[:n_new]) + [None] * (n_new - min(n_old, n_new))
+        for i, v in zip(indices, vals):
+            sigma[i] = int(v)
+        out = Tag()
+        out.sigma = sigma
+        return out
+
+    def _plan_update(self, state, blocks, length):
+        """What update() checks before any GPU work: (n', ascending blocks)."""
+        C = int(self.sectors) * self.sectorsize
+        n = int(state.chunks)
+        n_new = n if length is None else int(length) // C + 1
+        if length is not None and int(length) < 0:
+            raise HeartbeatError("length must not be negative")
+        listed = []
+        seen = set()
+        for index, data in blocks:
+            i = int(index)
+            if i < 0 or i >= n_new:
+                raise HeartbeatError("block index %d is outside the file's %d blocks" % (i, n_new))
+            if i in seen:
+                raise HeartbeatError("block index %d is listed twice" % i)
+            seen.add(i)
+            listed.append((i, bytes(data)))
+        if n_new != n:
+            for i in range(max(min(n, n_new) - 1, 0), n_new):
+                if i not in seen:
+                    raise HeartbeatError("block %d must be listed when the file goes from %d to %d blocks"
+                                         % (i, n, n_new))
+        listed.sort(key=lambda t: t[0])
+        for i, data in listed:
+            if i < n_new - 1:
+                if len(data) != C:
+                    raise HeartbeatError("block %d has %d bytes, not %d" % (i, len(data), C))
+            elif length is None:
+                if len(data) >= C:
+                    raise HeartbeatError("the last block %d has %d bytes, not fewer than %d" % (i, len(data), C))
+            elif len(data) != int(length) % C:
+                raise HeartbeatError("the last block %d has %d bytes, not %d" % (i, len(data), int(length) % C))
+        return n_new, listed
+
+    def _finish_update(self, tag, st, n_new, indices, raw):
+        new_tag = PySwizzle.patch_tag(tag, indices, Tag._from_raw(memoryview(raw), _native.width_of(int(self.prime))),
+                                      n_new)
+        new_state = State(st.f_key, st.alpha_key, n_new)
+        new_state.encrypt(self.key)
+        return new_tag, new_state
+
+    def update(self, tag, state, blocks, length=None):
+        """The tag and state of a file after an edit, an append or a
+        truncation, from the changed blocks alone: `blocks` is an iterable of
+        (index, new bytes), `length` the file's new length (None: the block
+        count stays state.chunks).  With C = sectors x sectorsize and n' =
+        length // C + 1: every listed block below n' - 1 must be C bytes, block
+        n' - 1 must be length % C bytes (any length below C without `length`);
+        an index >= n', a repeated index, or -- when n' differs from
+        state.chunks -- a missing index between min(n, n') - 1 and n' - 1
+        raises HeartbeatError naming the first such index, before any GPU work.
+        A file that grows therefore needs its old last block, with its new
+        bytes.  Returns (Tag, State): the tag with the listed values replaced
+        (patch_tag), and a state of n' chunks under the same f_key and
+        alpha_key, encrypted and signed with a fresh IV as encode returns it.
+        Neither argument is modified."""
+        self._check()
+        st = self._open_state(state)
+        n_new, listed = self._plan_update(st, blocks, length)
+        indices, data = self._pack_blocks(listed)
+        raw = encode_blocks_many(int(self.prime), int(self.sectors), [(st.f_key, st.alpha_key, indices, data)])[0]
+        return self._finish_update(tag, st, n_new, indices, raw)
+
+    def _file_blocks(self, state, fb, changed):
+        """(blocks, length) of update_file: the blocks the byte ranges touch
+        and those the length rule demands, read from the file's buffer."""
+        C = int(self.sectors) * self.sectorsize
+        length = fb.len
+        n, n_new = int(state.chunks), length // C + 1
+        want = set()
+        for off, nbytes in changed:
+            off, nbytes = int(off), int(nbytes)
+            if off < 0 or nbytes < 0 or off + nbytes > length:
+                raise HeartbeatError("range (%d, %d) is outside the file's %d bytes" % (off, nbytes, length))
+            if nbytes:
+                want.update(range(off // C, (off + nbytes - 1) // C + 1))
+        if n_new != n:
+            want.update(range(max(min(n, n_new) - 1, 0), n_new))
+        return [(i, fb.arr[i * C:min((i + 1) * C, length)].tobytes()) for i in sorted(want)], length
+
+    def update_file(self, tag, state, file, changed):
+        """update() from the new file itself: `changed` is a list of (offset,
+        nbytes) ranges of the NEW file that differ from the tagged one.  The
+        new length is the file's; the blocks re-tagged are those the ranges
+        touch plus the ones update()'s length rule demands.  The file is read
+        from its start and its position is left where it was."""
+        self._check()
+        fb = FileBuffer(file, from_start=True)
+        try:
+            blocks, length = self._file_blocks(state, fb, changed)
+        finally:
+            fb.restore()
+            fb.close()
+        return self.update(tag, state, blocks, length)
+
+    def update_many(self, items):
+        """update(tag, state, blocks, length) of every item of `items` in one
+        batched GPU call (hb_encode_blocks_many): [(Tag, State), ...], exactly
+        what a loop of update() returns, and the HeartbeatError of the first
+        item a loop would raise it for, before any GPU work.  Items whose key
+        length differs from the first one's, and a batch of fewer than
+        UPDATE_MANY_MIN items, go through update() one by one."""
+        items = [(tag, state, list(blocks), length) for tag, state, blocks, length in items]
+        self._check()
+        pre = []
+        for tag, state, blocks, length in items:
+            st = self._open_state(state)
+            n_new, listed = self._plan_update(st, blocks, length)
+            indices, data = self._pack_blocks(listed)
+            pre.append((st, n_new, indices, data))
+        if len(items) < UPDATE_MANY_MIN:
+            return [self.update(*item) for item in items]
+        klen = (len(_kb(pre[0][0].f_key)), len(_kb(pre[0][0].alpha_key))) if pre else None
+        batch = [k for k, t in enumerate(pre) if (len(_kb(t[0].f_key)), len(_kb(t[0].alpha_key))) == klen
+                 and klen[0] == klen[1]]
+        raws = encode_blocks_many(int(self.prime), int(self.sectors),
+                                  [(pre[k][0].f_key, pre[k][0].alpha_key, pre[k][2], pre[k][3]) for k in batch])
+        out = [None] * len(items)
+        for k, raw in zip(batch, raws):
+            st, n_new, indices, _ = pre[k]
+            out[k] = self._finish_update(items[k][0], st, n_new, indices, raw)
+        for k, item in enumerate(items):
+            if out[k] is None:
+                out[k] = self.update(*item)
         return out
 
     def gen_challenge(self, state):
@@ -658,6 +883,26 @@ def encode_files_mixed(items):
     is read from its current position to EOF and left there.  Runs on
     multi.primary_context() (a batch is not spread over several GPUs)."""
     return _many.encode_files_mixed(items, "hb_encode_mixed", Tag, open_first=False)
+
+
+# Fewest items PySwizzle.update_many sends through hb_encode_blocks_many; below
+# it the items go through update() one by one: the smallest item count at
+# which the batch's slowest round beats the loop's fastest, device-resident and
+# from host memory (the rule of ENCODE_MIXED_MIN).  One item is the same call
+# either way (1024-bit, S = 10, 4 blocks per file: 0.63-0.66 against 0.63-0.66
+# ms from host memory, 0.63-0.65 against 0.62-0.64 on the device); two items
+# win in both (0.64-0.67 against 1.19-1.21 ms; 0.63-0.67 against 1.17-1.21),
+# three by 2.5x, 256 by 90x (1.28-1.37 against 123.6-123.8 ms): the many rows
+# of scripts/blocks_rate.py, profiles/many/blocks_rate.json, DESIGN.md 5.3k.
+UPDATE_MANY_MIN = 2
+
+
+def encode_blocks_many(p, sectors, items):
+    """Batched GPU tags of listed blocks (hb_encode_blocks_many): `items` is a
+    list of (f_key, alpha_key, indices, data) with each file's listed blocks
+    back to back in `data`; returns one uint8 array of tag images per item.
+    Runs on multi.primary_context()."""
+    return _many.encode_blocks_many(p, sectors, items)
 
 
 # Fewest proofs PySwizzle.prove_many sends through hb_prove_many; below it the

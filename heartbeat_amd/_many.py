@@ -137,6 +137,45 @@ def encode_files_mixed(items, native, Tag, open_first):
     return [(Tag._from_raw(memoryview(out), w), nblocks) for out, nblocks, w in outs]
 
 
+def encode_blocks_many(p, sectors, items, native="hb_encode_blocks_many"):
+    """The tag images of listed blocks in one call of hb_encode_blocks_many:
+    `items` is a list of (f_key, alpha_key, indices, data) -- the block indices
+    of one file in any order and those blocks' bytes back to back, all of them
+    whole but possibly the last.  Returns one uint8 array of
+    len(indices) * width(p) bytes per item, the tag values in the order of its
+    indices.  All keys of a call have one length.  Runs on
+    multi.primary_context()."""
+    p = int(p)
+    sectors = int(sectors)
+    _check(p, sectors)
+    keep = []
+    for fk, ak, indices, data in items:
+        fk, ak = _kb(fk), _kb(ak)
+        idx = np.array([int(i) for i in indices], dtype=np.uint64)
+        keep.append((fk, ak, idx, np.frombuffer(bytes(data), dtype=np.uint8)))
+    if len({len(k) for t in keep for k in t[:2]}) > 1:
+        raise HeartbeatError("all f_keys and alpha_keys of a batch must have the same length")
+    if not keep:
+        return []
+    w = _native.width_of(p)
+    descs = (_native.BlocksDesc * len(keep))()
+    outs = []
+    for d, (fk, ak, idx, arr) in zip(descs, keep):
+        out = np.empty(len(idx) * w, dtype=np.uint8)
+        outs.append(out)
+        d.f_key, d.alpha_key = fk, ak
+        d.indices, d.nblocks = (idx.ctypes.data if len(idx) else None), len(idx)
+        d.data, d.len = (arr.ctypes.data if len(arr) else None), len(arr)
+        d.tags = out.ctypes.data if len(idx) else None
+    ctx = multi.primary_context()
+    pb = _native.be(p)
+    tries = ctypes.c_uint64()
+    with ctx.lock:
+        ctx.check(getattr(_native.lib(), native)(ctx.h, pb, len(pb), sectors, len(keep[0][0]), descs, len(keep), 0,
+                                                 ctypes.byref(tries)))
+    return outs
+
+
 def prove_files(native, p, sectors, items):
     """[(mu list, sigma), ...] of `items` = (chal_key, chunks, v_max, tag,
     file).  Every file is read whole, from its start (absolute offsets, as the

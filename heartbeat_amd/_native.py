@@ -50,6 +50,13 @@ class FileDesc(ctypes.Structure):
                 ("len", ctypes.c_uint64), ("tags", ctypes.c_void_p)]
 
 
+class BlocksDesc(ctypes.Structure):
+    """hb_blocks_desc (hbswizzle.h): one file's listed blocks of an hb_encode_blocks_many call."""
+    _fields_ = [("f_key", ctypes.c_char_p), ("alpha_key", ctypes.c_char_p), ("indices", ctypes.c_void_p),
+                ("nblocks", ctypes.c_uint64), ("data", ctypes.c_void_p), ("len", ctypes.c_uint64),
+                ("tags", ctypes.c_void_p)]
+
+
 class VerifyDesc(ctypes.Structure):
     """hb_verify_desc (hbswizzle.h): one proof of an hb_verify_rhs_many batch."""
     _fields_ = [("f_key", ctypes.c_char_p), ("alpha_key", ctypes.c_char_p), ("chal_key", ctypes.c_char_p),
@@ -161,6 +168,10 @@ SIGNATURES = [
                              _c.POINTER(_c.c_uint64)]),
     ("hb_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
                                   _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_encode_blocks_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(BlocksDesc),
+                                         _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_encode_blocks", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t, _P, _c.c_uint64,
+                                    _P, _c.c_uint64, _P, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_cxx_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
                                       _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,

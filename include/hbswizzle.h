@@ -128,7 +128,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_WIDE_SYNC_ALPHA 2097152u /* HB_WIDE_SYNC_ALPHA: the split encode computes alpha and its digit table on the compute stream, before the PRF passes, instead of beside them */
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
-#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode */
+#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode; hb_encode_blocks_many puts at most n listed blocks into one group and continues a longer list in the next */
 #define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many, hb_prove_many and their cxx counterparts put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
 uint32_t hb_test_switches(void);
 
@@ -472,6 +472,54 @@ typedef struct hb_file_desc {
 int hb_encode_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
                    size_t key_len, const hb_file_desc *files, uint64_t nfiles,
                    uint32_t flags, uint64_t *tries_out);
+
+/* Swizzle tags of listed blocks: the blocks an edit or an append changed, of
+ * one file or of many files each under its own keys, in one call.
+ * Replaces a caller's loop over the body of heartbeat/PySwizzle/PySwizzle.py:296-309
+ * for chosen values of i: tag_i = F(i) + sum_j alpha_j m_ij mod p depends on
+ * nothing but block i and its index, so a changed block needs neither the rest
+ * of the file nor fresh keys.  tags[k] of a file are exactly the bytes that
+ * hb_encode writes for block_base = indices[k], data + k*C, len_k =
+ * min(C, len - k*C) and nblocks = 1, with C = sectors * ss: the listed blocks
+ * lie back to back at `data`, all of them C bytes but possibly the last, whose
+ * short sector is the big-endian integer of the bytes it has, whose later
+ * sectors are 0 (PySwizzle.py:304-306), and which, when empty, gives
+ * tag = F(index).  indices may come in any order and may repeat; every value up
+ * to 2^64 - 1 is accepted (F hashes the index's decimal string).  One prime,
+ * one `sectors` and one key_len (16, 24 or 32) for the batch.  A group of lists
+ * is one copy up (indices, key schedules and host data together), one PRF
+ * launch (F(indices[k]) of every listed block and alpha_j of every file, each
+ * under its file's schedules), hb_encode_many's MAC launch over the packed
+ * blocks, and one copy down; the runtime splits a call, and a single list,
+ * whose device scratch would pass the batches' cap ($HB_TEST_BATCH_BLOCKS: at
+ * that many listed blocks).
+ * flags: HB_DATA_ON_DEVICE / HB_TAGS_ON_DEVICE (device pointers of any
+ * alignment); any other flag, HB_PRF_CXX and HB_ASYNC among them, returns
+ * HB_EUNSUPPORTED.  Every descriptor is checked before any GPU work and
+ * hb_last_error names the file ("file 3: ..."): a NULL key, NULL indices or
+ * tags with nblocks > 0, a len outside [(nblocks - 1) * C, nblocks * C] (0 for
+ * nblocks == 0), or NULL data with len > 0 returns HB_EINVAL and no tag buffer
+ * is written.  nfiles == 0 and nblocks == 0 are no-ops.  *tries_out (may be
+ * NULL) receives the sum of the listed blocks' F tries: what those single
+ * hb_encode calls report in total. */
+typedef struct hb_blocks_desc {
+    const uint8_t *f_key, *alpha_key;  /* key_len bytes each */
+    const uint64_t *indices;           /* host, nblocks block indices: any order, repeats allowed */
+    uint64_t nblocks;
+    const uint8_t *data;               /* listed block k at data + k*C; host, or device with HB_DATA_ON_DEVICE */
+    uint64_t len;                      /* (nblocks-1)*C <= len <= nblocks*C: only the LAST listed block may be short */
+    uint8_t *tags;                     /* nblocks * hb_width(p) bytes; host, or device with HB_TAGS_ON_DEVICE */
+} hb_blocks_desc;
+
+int hb_encode_blocks_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                          size_t key_len, const hb_blocks_desc *files, uint64_t nfiles,
+                          uint32_t flags, uint64_t *tries_out);
+
+/* hb_encode_blocks_many for one file (nfiles = 1; errors read "file 0: ..."). */
+int hb_encode_blocks(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                     const uint8_t *f_key, const uint8_t *alpha_key, size_t key_len,
+                     const uint64_t *indices, uint64_t nblocks, const uint8_t *data, uint64_t len,
+                     uint8_t *tags, uint32_t flags, uint64_t *tries_out);
 
 /* hb_encode_many for the cxx Swizzle (heartbeat.Heartbeat): many whole files,
  * each under its own keys, in one call.
