@@ -289,6 +289,116 @@ extern "C" int emul_encode(const uint8_t *p_be, size_t plen, uint32_t S, const u
     return -2;
 }
 
+// ------------------------------------------------------------------ mod p
+// The shared lane arithmetic on caller-supplied little-endian limbs
+// (tests/test_modarith_emul.py compares with Python ints).  Every entry takes
+// the limb count nl (2, 8, 16, 32 or 64), the modulus p (nl limbs, odd) and n
+// operand sets, builds ModP the way the runtime's make_mod does and calls the
+// unmodified hb_lane.hpp functions.  Returns 0, or -2 for another nl.
+template <int NL>
+static ModP<NL> lane_mod(const uint32_t *p, Limbs &pl) {
+    pl.assign(p, p + NL);
+    ModP<NL> M;
+    memset(&M, 0, sizeof M);
+    for (int t = 0; t < NL; ++t) M.p[t] = p[t];
+    M.pinv = mont_pinv(p[0]);
+    M.inv_scaled = inv_scaled(pl);
+    return M;
+}
+
+// out_k = a_k b_k R^-1 mod p: hb_mac + hb_redc + hb_reduce_small as
+// hb_block_tag chains them (a in alpha_mont's place, b in the sector's).
+template <int NL>
+static int emul_mont_mul_t(const uint32_t *p, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out) {
+    Limbs pl;
+    const ModP<NL> M = lane_mod<NL>(p, pl);
+    for (uint32_t k = 0; k < n; ++k) {
+        u32 acc[2 * NL + 1], v[NL + 1], bb[NL];
+        for (int t = 0; t <= 2 * NL; ++t) acc[t] = 0;
+        for (int t = 0; t < NL; ++t) bb[t] = b[(size_t)k * NL + t];
+        hb_mac<NL>(acc, a + (size_t)k * NL, bb);
+        hb_redc<NL>(acc, M, v);
+        hb_reduce_small<NL>(v, M, out + (size_t)k * NL);
+    }
+    return 0;
+}
+
+// out_k = x_k R mod p (hb_to_mont with R^2 mod p from the host helper).
+template <int NL>
+static int emul_to_mont_t(const uint32_t *p, uint32_t n, const uint32_t *x, uint32_t *out) {
+    Limbs pl;
+    const ModP<NL> M = lane_mod<NL>(p, pl);
+    const Limbs r2 = pow2_mod(64u * NL, pl);
+    for (uint32_t k = 0; k < n; ++k) {
+        u32 xx[NL];
+        for (int t = 0; t < NL; ++t) xx[t] = x[(size_t)k * NL + t];
+        hb_to_mont<NL>(xx, r2.data(), M, out + (size_t)k * NL);
+    }
+    return 0;
+}
+
+// out_k = v_k mod p for v_k of NL + 1 limbs (hb_reduce_small alone).
+template <int NL>
+static int emul_reduce_small_t(const uint32_t *p, uint32_t n, const uint32_t *v, uint32_t *out) {
+    Limbs pl;
+    const ModP<NL> M = lane_mod<NL>(p, pl);
+    for (uint32_t k = 0; k < n; ++k) {
+        u32 vv[NL + 1];
+        for (int t = 0; t <= NL; ++t) vv[t] = v[(size_t)k * (NL + 1) + t];
+        hb_reduce_small<NL>(vv, M, out + (size_t)k * NL);
+    }
+    return 0;
+}
+
+// hb_block_tag's shape: acc = F R + sum_{j < S} a_j b_j in the 2 NL + 1 limb
+// accumulator, ONE hb_redc and ONE hb_reduce_small:
+// out = (F + sum_j a_j b_j R^-1) mod p.
+template <int NL>
+static int emul_mac_sum_t(const uint32_t *p, uint32_t S, const uint32_t *a, const uint32_t *b, const uint32_t *F,
+                          uint32_t *out) {
+    Limbs pl;
+    const ModP<NL> M = lane_mod<NL>(p, pl);
+    u32 acc[2 * NL + 1], v[NL + 1];
+    for (int t = 0; t < NL; ++t) { acc[t] = 0; acc[NL + t] = F[t]; }
+    acc[2 * NL] = 0;
+    for (uint32_t j = 0; j < S; ++j) {
+        u32 bb[NL];
+        for (int t = 0; t < NL; ++t) bb[t] = b[(size_t)j * NL + t];
+        hb_mac<NL>(acc, a + (size_t)j * NL, bb);
+    }
+    hb_redc<NL>(acc, M, v);
+    hb_reduce_small<NL>(v, M, out);
+    return 0;
+}
+
+#define EMUL_BY_NL(fn, ...)                         \
+    switch (nl) {                                   \
+    case 2: return fn<2>(__VA_ARGS__);              \
+    case 8: return fn<8>(__VA_ARGS__);              \
+    case 16: return fn<16>(__VA_ARGS__);            \
+    case 32: return fn<32>(__VA_ARGS__);            \
+    case 64: return fn<64>(__VA_ARGS__);            \
+    default: return -2;                             \
+    }
+
+extern "C" int emul_mont_mul(int nl, const uint32_t *p, uint32_t n, const uint32_t *a, const uint32_t *b,
+                             uint32_t *out) {
+    EMUL_BY_NL(emul_mont_mul_t, p, n, a, b, out)
+}
+
+extern "C" int emul_to_mont(int nl, const uint32_t *p, uint32_t n, const uint32_t *x, uint32_t *out) {
+    EMUL_BY_NL(emul_to_mont_t, p, n, x, out)
+}
+
+extern "C" int emul_reduce_small(int nl, const uint32_t *p, uint32_t n, const uint32_t *v, uint32_t *out) {
+    EMUL_BY_NL(emul_reduce_small_t, p, n, v, out)
+}
+
+extern "C" int emul_mac_sum(int nl, const uint32_t *p, uint32_t S, const uint32_t *a, const uint32_t *b,
+                            const uint32_t *F, uint32_t *out) {
+    EMUL_BY_NL(emul_mac_sum_t, p, S, a, b, F, out)
+}
+
 // ------------------------------------------------------------------ cxx prf
 // One lane's cxx prf::evaluate (hb_cxx_try + SHA256(LE32)), as hb_engine<MODE 1>
 // runs it -- or hb_cxx_try_bytes (MODE 2) when ByteCount(limit) % 16 != 0:

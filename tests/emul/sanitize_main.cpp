@@ -18,6 +18,11 @@ int emul_encode(const uint8_t *p_be, size_t plen, uint32_t S, const uint8_t *fke
                 uint8_t *tags, int lane, int align, int use_prefix);
 int emul_cxx_prf(const uint8_t *key, size_t keylen, const uint8_t *range_be, size_t rlen, uint32_t x,
                  uint8_t *out_be, int lane);
+int emul_mont_mul(int nl, const uint32_t *p, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);
+int emul_to_mont(int nl, const uint32_t *p, uint32_t n, const uint32_t *x, uint32_t *out);
+int emul_reduce_small(int nl, const uint32_t *p, uint32_t n, const uint32_t *v, uint32_t *out);
+int emul_mac_sum(int nl, const uint32_t *p, uint32_t S, const uint32_t *a, const uint32_t *b, const uint32_t *F,
+                 uint32_t *out);
 int hbo_prf_eval(const unsigned char *key, size_t keylen, const unsigned char *range_be, size_t range_len,
                  uint64_t x, unsigned char *out_be, size_t out_len);
 int hbo_cxx_prf_eval(const unsigned char *key, size_t keylen, const unsigned char *range_be,
@@ -108,6 +113,42 @@ int main() {
                       (unsigned long long)len, align);
             }
         }
+    }
+    // the lane arithmetic entries on p = 2^(32 nl) - c, the largest prime of
+    // each full width (R mod p = c, so c is 1 in Montgomery form), with
+    // operands that are not below p and hb_reduce_small's last input 2^32 p - 1
+    const struct { int nl; uint32_t c; } full[] = {{2, 59}, {8, 189}, {16, 569}, {32, 105}, {64, 1557}};
+    for (const auto &f : full) {
+        const int nl = f.nl;
+        const uint32_t c = f.c;
+        std::vector<uint32_t> p(nl, 0xffffffffu), one(nl, 0), top(nl, 0xffffffffu), out(nl);
+        p[0] = 0u - c;
+        one[0] = c;
+        auto is_small = [&](const std::vector<uint32_t> &v, uint32_t x) {
+            for (int t = 1; t < nl; ++t)
+                if (v[t]) return false;
+            return v[0] == x;
+        };
+        // R - 1 = p + c - 1 in Montgomery form: (c - 1) c
+        CHECK(emul_to_mont(nl, p.data(), 1, top.data(), out.data()) == 0 && is_small(out, (c - 1) * c),
+              "to_mont nl=%d", nl);
+        // 1 (as c) times R - 1: (R - 1) mod p = c - 1
+        CHECK(emul_mont_mul(nl, p.data(), 1, one.data(), top.data(), out.data()) == 0 && is_small(out, c - 1),
+              "mont_mul nl=%d", nl);
+        // 2^32 p - 1 -> p - 1
+        std::vector<uint32_t> v(nl + 1, 0xffffffffu), pm1(p);
+        v[1] = 0xffffffffu - c;
+        pm1[0] -= 1;
+        CHECK(emul_reduce_small(nl, p.data(), 1, v.data(), out.data()) == 0 && out == pm1, "reduce_small nl=%d", nl);
+        // F = p - 1 plus three products 1 (R - 1): p - 1 + 3 (c - 1) = 3 c - 4 mod p
+        std::vector<uint32_t> a3, b3;
+        for (int j = 0; j < 3; ++j) {
+            a3.insert(a3.end(), one.begin(), one.end());
+            b3.insert(b3.end(), top.begin(), top.end());
+        }
+        CHECK(emul_mac_sum(nl, p.data(), 3, a3.data(), b3.data(), pm1.data(), out.data()) == 0 &&
+                  is_small(out, 3 * c - 4),
+              "mac_sum nl=%d", nl);
     }
     printf("sanitize: %d failures\n", fails);
     return fails ? 1 : 0;
