@@ -31,7 +31,7 @@ import os
 
 import numpy as np
 
-from .. import _many, _native, multi
+from .. import _blocks, _many, _native, multi
 from .._filebuf import FileBuffer
 from ..exc import HeartbeatError
 from ..primes import getPrimes
@@ -121,6 +121,12 @@ class Tag(object):
         t._sigma = None
         t._raw = raw
         t._width = width
+        return t
+
+    @classmethod
+    def _from_sigma(cls, sigma):
+        t = cls()
+        t.sigma = sigma
         return t
 
     @property
@@ -346,17 +352,7 @@ class PySwizzle(object):
     def _sorted_blocks(self, blocks):
         """[(index, bytes)] in ascending order of index; every index once and
         inside [0, 2^64)."""
-        out, seen = [], set()
-        for index, data in blocks:
-            i = int(index)
-            if i < 0 or i >> 64:
-                raise HeartbeatError("block index %d is outside [0, 2^64)" % i)
-            if i in seen:
-                raise HeartbeatError("block index %d is listed twice" % i)
-            seen.add(i)
-            out.append((i, bytes(data)))
-        out.sort(key=lambda t: t[0])
-        return out
+        return _blocks.sorted_blocks(blocks, 64)
 
     def _open_state(self, state):
         """A decrypted copy of `state` (its signature checked); the argument
@@ -368,11 +364,7 @@ class PySwizzle(object):
     def _pack_blocks(self, blocks):
         """(indices, packed bytes) of ascending blocks for one descriptor of
         hb_encode_blocks_many: all blocks whole but possibly the last."""
-        C = int(self.sectors) * self.sectorsize
-        for k, (i, data) in enumerate(blocks):
-            if len(data) > C or (len(data) < C and k + 1 < len(blocks)):
-                raise HeartbeatError("block %d has %d bytes, not %d" % (i, len(data), C))
-        return [i for i, _ in blocks], b"".join(d for _, d in blocks)
+        return _blocks.pack_blocks(int(self.sectors) * self.sectorsize, blocks)
 
     def encode_blocks(self, state, blocks):
         """New tag values of listed blocks under the state's keys: `blocks` is
@@ -399,78 +391,11 @@ class PySwizzle(object):
         ints.  A longer result must have every added index listed; a shorter
         one drops the rest.  A tag that holds its fixed-width image keeps one;
         a tag built from a list (fromdict) stays a list."""
-        n_old = len(tag)
-        n_new = n_old if nblocks is None else int(nblocks)
-        indices = [int(i) for i in indices]
-        if len(indices) != len(values):
-            raise HeartbeatError("%d indices for %d values" % (len(indices), len(values)))
-        for i in indices:
-            if i < 0 or i >= n_new:
-                raise HeartbeatError("block index %d is outside the tag's %d blocks" % (i, n_new))
-        listed = set(indices)
-        for i in range(n_old, n_new):
-            if i not in listed:
-                raise HeartbeatError("block %d is added but not listed" % i)
-        if tag._sigma is None:
-            w = tag._width
-            if isinstance(values, Tag) and values._sigma is None and values._width == w:
-                vraw = bytes(values._raw)
-            else:
-                vals = values.sigma if isinstance(values, Tag) else list(values)
-                try:
-                    vraw = b"".join(int(v).to_bytes(w, "big") for v in vals)
-                except OverflowError:
-                    raise HeartbeatError("a tag value does not fit the tag's %d bytes" % w)
-            # one copy of the image: the kept values, then the listed ones over it
-            keep = min(n_old, n_new) * w
-            img = np.zeros(n_new * w, dtype=np.uint8)
-            img[:keep] = np.frombuffer(tag._raw, dtype=np.uint8)[:keep]
-            vals = np.frombuffer(vraw, dtype=np.uint8).reshape(len(indices), w) if indices else None
-            rows = img.reshape(n_new, w)
-            for k, i in enumerate(indices):
-                rows[i] = vals[k]
-            return Tag._from_raw(memoryview(img), w)
-        vals = values.sigma if isinstance(values, Tag) else list(values)
-        sigma = list(tag.sigma[:n_new]) + [None] * (n_new - min(n_old, n_new))
-        for i, v in zip(indices, vals):
-            sigma[i] = int(v)
-        out = Tag()
-        out.sigma = sigma
-        return out
+        return _blocks.patch_tag(Tag, tag, indices, values, nblocks)
 
     def _plan_update(self, state, blocks, length):
         """What update() checks before any GPU work: (n', ascending blocks)."""
-        C = int(self.sectors) * self.sectorsize
-        n = int(state.chunks)
-        n_new = n if length is None else int(length) // C + 1
-        if length is not None and int(length) < 0:
-            raise HeartbeatError("length must not be negative")
-        listed = []
-        seen = set()
-        for index, data in blocks:
-            i = int(index)
-            if i < 0 or i >= n_new:
-                raise HeartbeatError("block index %d is outside the file's %d blocks" % (i, n_new))
-            if i in seen:
-                raise HeartbeatError("block index %d is listed twice" % i)
-            seen.add(i)
-            listed.append((i, bytes(data)))
-        if n_new != n:
-            for i in range(max(min(n, n_new) - 1, 0), n_new):
-                if i not in seen:
-                    raise HeartbeatError("block %d must be listed when the file goes from %d to %d blocks"
-                                         % (i, n, n_new))
-        listed.sort(key=lambda t: t[0])
-        for i, data in listed:
-            if i < n_new - 1:
-                if len(data) != C:
-                    raise HeartbeatError("block %d has %d bytes, not %d" % (i, len(data), C))
-            elif length is None:
-                if len(data) >= C:
-                    raise HeartbeatError("the last block %d has %d bytes, not fewer than %d" % (i, len(data), C))
-            elif len(data) != int(length) % C:
-                raise HeartbeatError("the last block %d has %d bytes, not %d" % (i, len(data), int(length) % C))
-        return n_new, listed
+        return _blocks.plan_update(int(self.sectors) * self.sectorsize, state.chunks, blocks, length)
 
     def _finish_update(self, tag, st, n_new, indices, raw):
         new_tag = PySwizzle.patch_tag(tag, indices, Tag._from_raw(memoryview(raw), _native.width_of(int(self.prime))),
@@ -504,19 +429,7 @@ class PySwizzle(object):
     def _file_blocks(self, state, fb, changed):
         """(blocks, length) of update_file: the blocks the byte ranges touch
         and those the length rule demands, read from the file's buffer."""
-        C = int(self.sectors) * self.sectorsize
-        length = fb.len
-        n, n_new = int(state.chunks), length // C + 1
-        want = set()
-        for off, nbytes in changed:
-            off, nbytes = int(off), int(nbytes)
-            if off < 0 or nbytes < 0 or off + nbytes > length:
-                raise HeartbeatError("range (%d, %d) is outside the file's %d bytes" % (off, nbytes, length))
-            if nbytes:
-                want.update(range(off // C, (off + nbytes - 1) // C + 1))
-        if n_new != n:
-            want.update(range(max(min(n, n_new) - 1, 0), n_new))
-        return [(i, fb.arr[i * C:min((i + 1) * C, length)].tobytes()) for i in sorted(want)], length
+        return _blocks.file_blocks(int(self.sectors) * self.sectorsize, state.chunks, fb, changed)
 
     def update_file(self, tag, state, file, changed):
         """update() from the new file itself: `changed` is a list of (offset,

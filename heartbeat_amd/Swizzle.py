@@ -36,7 +36,7 @@ import struct
 
 import numpy as np
 
-from . import _many, _native, multi
+from . import _blocks, _many, _native, multi
 from ._filebuf import FileBuffer
 from .exc import HeartbeatError
 from .PySwizzle.PySwizzle import _kb, _random_bytes, getPrime
@@ -166,6 +166,12 @@ class Tag(_Serializable):
         t._sigma = None
         t._raw = raw
         t._width = width
+        return t
+
+    @classmethod
+    def _from_sigma(cls, sigma):
+        t = cls()
+        t._sigma = sigma
         return t
 
     @property
@@ -509,6 +515,131 @@ class Swizzle(_Serializable):
             out.append((tag, state))
         return out
 
+    # -- re-tagging listed blocks after an edit or an append
+    def _open_state(self, state):
+        """A decrypted copy of `state`; the argument is left as it was.  A bad
+        signature raises: the reference's decrypt ignores it (Swizzle.hxx:383-406),
+        but tags made under garbage keys would corrupt a tag silently."""
+        s = state._copy()
+        if not s._check_sig_and_decrypt(self.k_enc, self.k_mac):
+            raise HeartbeatError("Signature check or decryption failed in updating tags.  "
+                                 "State of remote file cannot be verified.")
+        return s
+
+    def _block_bytes(self):
+        return int(self.sectors) * int(self.sectorsize)
+
+    def encode_blocks(self, state, blocks):
+        """New tag values of listed blocks under the state's keys: `blocks` is
+        an iterable of (index, bytes).  Returns (indices, Tag): the indices in
+        ascending order and a Tag holding each block's sigma
+        (shacham_waters_private.cxx:674-694 for chunk_id = index), in that
+        order -- the patch an owner sends to the server (patch_tag).  Every
+        block must be whole (sectors x sectorsize bytes) except the one of the
+        highest index, which may be short; an empty one keeps f(index)
+        unreduced (:681-690).  An index is the prf's unsigned int: below 2^32.
+        The state's signature is checked and a copy is decrypted; the argument
+        is left as it was."""
+        self._check()
+        st = self._open_state(state)
+        indices, data = _blocks.pack_blocks(self._block_bytes(), _blocks.sorted_blocks(blocks, 32))
+        raw = encode_blocks_many(self.prime, self.sectors, [(st.f_key, st.alpha_key, indices, data)])[0]
+        return indices, Tag._from_raw(memoryview(raw), _native.width_of(self.prime))
+
+    @staticmethod
+    def patch_tag(tag, indices, values, nblocks=None):
+        """A new Tag of `nblocks` values (default len(tag)): those of `tag`
+        with values[k] in place of block indices[k].  No key is needed: this is
+        the server's side of an update.  `values` is a Tag or a sequence of
+        ints.  A longer result must have every added index listed; a shorter
+        one drops the rest.  A tag that holds its fixed-width image keeps one
+        (one numpy copy); a tag built from a list (fromdict) stays a list."""
+        return _blocks.patch_tag(Tag, tag, indices, values, nblocks)
+
+    def _plan_update(self, st, blocks, length):
+        """What update() checks before any GPU work, on the opened state:
+        (n', indices, packed bytes)."""
+        C = self._block_bytes()
+        if length is not None and int(length) // C + 1 >= 1 << 32:
+            raise HeartbeatError("a file of %d blocks does not fit the state's 32-bit block count"
+                                 % (int(length) // C + 1))
+        n_new, listed = _blocks.plan_update(C, st.n, blocks, length)
+        indices, data = _blocks.pack_blocks(C, listed)
+        return n_new, indices, data
+
+    def _finish_update(self, tag, st, n_new, indices, raw):
+        new_tag = Swizzle.patch_tag(tag, indices, Tag._from_raw(memoryview(raw), _native.width_of(self.prime)), n_new)
+        new_state = State()
+        new_state.n, new_state.f_key, new_state.alpha_key = n_new, st.f_key, st.alpha_key
+        new_state.encrypt(self.k_enc, self.k_mac)
+        return new_tag, new_state
+
+    def update(self, tag, state, blocks, length=None):
+        """The tag and state of a file after an edit, an append or a
+        truncation, from the changed blocks alone: `blocks` is an iterable of
+        (index, new bytes), `length` the file's new length (None: the block
+        count stays state.n).  With C = sectors x sectorsize and n' =
+        length // C + 1: every listed block below n' - 1 must be C bytes, block
+        n' - 1 must be length % C bytes (any length below C without `length`);
+        an index >= n', a repeated index, or -- when n' differs from state.n --
+        a missing index between min(n, n') - 1 and n' - 1 raises
+        HeartbeatError naming the first such index, and so do a state whose
+        signature does not check and n' >= 2^32 (the state's n is a u32), all
+        before any GPU work.  A file that grows therefore needs its old last
+        block, with its new bytes.  Returns (Tag, State): the tag with the
+        listed values replaced (patch_tag), and a state of n' blocks under the
+        same f_key and alpha_key, encrypted and signed with a fresh IV as
+        encode returns it.  Neither argument is modified."""
+        self._check()
+        st = self._open_state(state)
+        n_new, indices, data = self._plan_update(st, blocks, length)
+        raw = encode_blocks_many(self.prime, self.sectors, [(st.f_key, st.alpha_key, indices, data)])[0]
+        return self._finish_update(tag, st, n_new, indices, raw)
+
+    def update_file(self, tag, state, file, changed):
+        """update() from the new file itself: `changed` is a list of (offset,
+        nbytes) ranges of the NEW file that differ from the tagged one.  The
+        new length is the file's; the blocks re-tagged are those the ranges
+        touch plus the ones update()'s length rule demands.  The file is read
+        from its start and its position is left where it was."""
+        self._check()
+        fb = FileBuffer(file, from_start=True)
+        try:
+            blocks, length = _blocks.file_blocks(self._block_bytes(), state.n, fb, changed)
+        finally:
+            fb.restore()
+            fb.close()
+        return self.update(tag, state, blocks, length)
+
+    def update_many(self, items):
+        """update(tag, state, blocks, length) of every item of `items` in one
+        batched GPU call (hb_cxx_encode_blocks_many): [(Tag, State), ...],
+        exactly what a loop of update() returns, and the HeartbeatError of the
+        first item a loop would raise it for, before any GPU work.  Items whose
+        key length differs from the first one's, and a batch of fewer than
+        CXX_UPDATE_MANY_MIN items, go through update() one by one."""
+        items = [(tag, state, list(blocks), length) for tag, state, blocks, length in items]
+        self._check()
+        pre = []
+        for tag, state, blocks, length in items:
+            st = self._open_state(state)
+            pre.append((st,) + self._plan_update(st, blocks, length))
+        if len(items) < CXX_UPDATE_MANY_MIN:
+            return [self.update(*item) for item in items]
+        klen = (len(_kb(pre[0][0].f_key)), len(_kb(pre[0][0].alpha_key))) if pre else None
+        batch = [k for k, t in enumerate(pre) if (len(_kb(t[0].f_key)), len(_kb(t[0].alpha_key))) == klen
+                 and klen[0] == klen[1]]
+        raws = encode_blocks_many(self.prime, self.sectors,
+                                  [(pre[k][0].f_key, pre[k][0].alpha_key, pre[k][2], pre[k][3]) for k in batch])
+        out = [None] * len(items)
+        for k, raw in zip(batch, raws):
+            st, n_new, indices, _ = pre[k]
+            out[k] = self._finish_update(items[k][0], st, n_new, indices, raw)
+        for k, item in enumerate(items):
+            if out[k] is None:
+                out[k] = self.update(*item)
+        return out
+
     def gen_challenge(self, state):
         """l = (unsigned int)(check_fraction * n) indices, v limit p (:704-729)."""
         s = state._copy()   # `state s = s_enc` (:706)
@@ -817,6 +948,26 @@ def encode_files_mixed(items):
     before it are left at EOF as the loop leaves them and its error is raised.
     Runs on multi.primary_context()."""
     return _many.encode_files_mixed(items, "hb_cxx_encode_mixed", Tag, open_first=True)
+
+
+# Fewest items Swizzle.update_many sends through one hb_cxx_encode_blocks_many;
+# below it the items go through update() one by one.  One item is the same
+# call either way (update() itself is hb_cxx_encode_blocks_many with one
+# descriptor), so the batch starts at two: 1024-bit, S = 10, 4 blocks per file,
+# two files in one call take 0.195-0.214 ms from host memory where one file
+# takes 0.165-0.177 (0.199-0.222 against 0.173-0.187 device-resident), the
+# files rows of scripts/cxx_blocks_rate.py, profiles/many/cxx_blocks_rate.json,
+# DESIGN.md 5.3l.
+CXX_UPDATE_MANY_MIN = 2
+
+
+def encode_blocks_many(p, sectors, items):
+    """Batched GPU tags of listed blocks with the cxx prf
+    (hb_cxx_encode_blocks_many): `items` is a list of (f_key, alpha_key,
+    indices, data) with each file's listed blocks back to back in `data` and
+    every index below 2^32; returns one uint8 array of tag images per item.
+    Runs on multi.primary_context()."""
+    return _many.encode_blocks_many(p, sectors, items, native="hb_cxx_encode_blocks_many")
 
 
 # Fewest proofs Swizzle.prove_many sends through hb_cxx_prove_many, and

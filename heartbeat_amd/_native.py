@@ -174,6 +174,10 @@ SIGNATURES = [
                                     _P, _c.c_uint64, _P, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_cxx_encode_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(FileDesc),
                                       _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_cxx_encode_blocks_many", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _c.c_size_t, _c.POINTER(BlocksDesc),
+                                             _c.c_uint64, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
+    ("hb_cxx_encode_blocks", _c.c_int, [_P, _B, _c.c_size_t, _c.c_uint32, _B, _B, _c.c_size_t, _P, _c.c_uint64,
+                                        _P, _c.c_uint64, _P, _c.c_uint32, _c.POINTER(_c.c_uint64)]),
     ("hb_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,
                                    _c.POINTER(_c.c_uint64)]),
     ("hb_cxx_encode_mixed", _c.c_int, [_P, _c.POINTER(EncodeMixedDesc), _c.c_uint64, _c.c_uint32,

@@ -94,8 +94,11 @@ inline u64 hb_blocks_cost(const HbBatchSizes &z, const BlkShape &E, u64 seg_len,
 // Segments and groups, in the caller's order.  A group ends before the block
 // that would take it over cap_blocks listed blocks or cap_bytes of scratch; a
 // single block alone may pass cap_bytes (every block gets a group).
-inline HbBlkPlan hb_blocks_plan(const hb_blocks_desc *files, u64 nfiles, const HbBatchSizes &z, const BlkShape &E,
-                                u64 cap_blocks, u64 cap_bytes) {
+// seg_cost(file, first, n): scratch bytes of blocks [first, first + n) of that
+// file's list as one segment, growing with n (hb_blocks_cost here;
+// hb_cblocks_host.hpp has the cxx call's).
+template <class Cost>
+HbBlkPlan hb_blocks_plan_by(const hb_blocks_desc *files, u64 nfiles, u64 cap_blocks, u64 cap_bytes, Cost &&seg_cost) {
     HbBlkPlan P;
     if (cap_blocks < 1) cap_blocks = 1;
     HbBlkGroup G = {0, 0, 0, 0};
@@ -111,7 +114,7 @@ inline HbBlkPlan hb_blocks_plan(const hb_blocks_desc *files, u64 nfiles, const H
             if (room > left) room = left;
             if (room > HB_BLK_SEG_MAX) room = HB_BLK_SEG_MAX;
             const u64 bytes_left = cap_bytes > G.bytes ? cap_bytes - G.bytes : 0;
-            auto cost = [&](u64 n) { return hb_blocks_cost(z, E, hb_blocks_seg_len(files[i].len, E.C, first, n), n); };
+            auto cost = [&](u64 n) { return seg_cost(i, first, n); };
             // the most blocks whose segment still fits: the cost grows with the count
             u64 lo = 0, hi = room;
             while (lo < hi) {
@@ -136,6 +139,12 @@ inline HbBlkPlan hb_blocks_plan(const hb_blocks_desc *files, u64 nfiles, const H
     }
     close();
     return P;
+}
+inline HbBlkPlan hb_blocks_plan(const hb_blocks_desc *files, u64 nfiles, const HbBatchSizes &z, const BlkShape &E,
+                                u64 cap_blocks, u64 cap_bytes) {
+    return hb_blocks_plan_by(files, nfiles, cap_blocks, cap_bytes, [&](u64 i, u64 first, u64 n) {
+        return hb_blocks_cost(z, E, hb_blocks_seg_len(files[i].len, E.C, first, n), n);
+    });
 }
 
 // hb_encode_blocks_many:

@@ -42,6 +42,8 @@
 #include "hb_emixed_host.hpp"
 #include "hb_blocks_args.hpp"
 #include "hb_blocks_host.hpp"
+#include "hb_cblocks_args.hpp"
+#include "hb_cblocks_host.hpp"
 #include "hb_prime_host.hpp"
 #include "hb_merkle_host.hpp"
 #include "hb_onehash_host.hpp"
@@ -94,6 +96,8 @@ template <int NL> u32 hb_emixed_mac_threads();
 template <int NL> hipError_t hb_launch_emixed_mac(const EmMacArgs<NL> &, u32, u32, hipStream_t);
 // hb_kern_blocks.hip / hb_kern_blocks64.hip
 template <int NL> hipError_t hb_launch_blocks_prf(const BlocksPrfArgs<NL> &, int, int, hipStream_t);
+// hb_kern_cblocks.hip / hb_kern_cblocks64.hip
+template <int NL> hipError_t hb_launch_cblocks_prf(const CblkPrfArgs<NL> &, int, int, hipStream_t);
 // hb_prime.hpp (hb_kern_prime*.hip)
 template <int NL> hipError_t hb_launch_prime_test(const PrTestArgs &, bool, hipStream_t);
 template <int NL> hipError_t hb_launch_prime_sieve(const PrSieveArgs &, u32, u32, hipStream_t);
@@ -2124,6 +2128,95 @@ int cxx_encode_many_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const Pri
         c->ph_valid = false;
         return 0;
     });
+    if (rc) return rc;
+    if (tries_out) *tries_out = tries;
+    return 0;
+}
+
+// ------------------------------------------------------------------ cxx listed-block encode
+// hb_cxx_encode_blocks_many: encode_blocks_impl for the cxx Swizzle.  The host
+// header (hb_cblocks_host.hpp) cuts the lists into segments and groups, queues
+// each group's wave-jobs longest first and fills its staging buffer; a group
+// is cxx_encode_many_impl's round trip -- one H2D copy (schedules, records,
+// wave-jobs, workgroups, u32 indices, host blocks), hb_cblocks_prf_kernel (F
+// at the listed indices and alpha, raw; the block that reads no sector keeps
+// its unreduced F as its tag), hb_mont_kernel in place over the group's alpha
+// tables, the batched encode's MAC launch unchanged over the packed blocks
+// that read a sector (none: no MAC launch), one D2H copy.  Nothing falls
+// through to the single encode: a long list is several segments.
+template <int NL>
+int cxx_encode_blocks_impl(hb_ctx *c, const uint8_t *p_be, size_t p_len, const PrimeInfo &pi, u32 S, size_t key_len,
+                           const hb_blocks_desc *files, u64 nfiles, u32 flags, u64 *tries_out) {
+    const Limbs p = from_be(p_be, p_len, NL);
+    const HbBatchSizes z = batch_sizes<NL>();
+    const u64 C = (u64)pi.ss * S;
+    const BlkShape B = {C, S, pi.tw, hb_batch_mac_bpw<NL>(S), (flags & HB_DATA_ON_DEVICE) != 0,
+                        (flags & HB_TAGS_ON_DEVICE) != 0, full16(pi, NL, C, nullptr)};
+    const int nr = aes_rounds(key_len);
+    const HbCblkPlan plan =
+        hb_cblocks_plan(files, nfiles, z, B, hb_test_cap(sw_env(c, "HB_TEST_BATCH_BLOCKS")), HB_BATCH_BYTES);
+    PrfParams<NL> P0;
+    if (int rc = batch_begin<NL>(c, files[0].f_key, key_len, p_be, p_len, &P0)) return rc;
+    u64 tries = 0;
+
+    auto run_group = [&](size_t g) -> int {
+        const HbBlkGroup &G = plan.blk.groups[g];
+        const HbBlkTotals T = hb_cblocks_totals(files, plan.blk, G, B, plan.cb.groups[g].njobs);
+        const HbArena L = hb_cblocks_arena(z, B, G, T);
+        if (int rc = group_arenas(c, L, HB_CBK_TAGS)) return rc;
+        uint8_t *dev = (uint8_t *)c->bdev.p, *host = (uint8_t *)c->bhost.p;
+        u64 bad = 0;
+        if (!hb_cblocks_fill<NL>(files, plan, g, B, L, P0, key_len, nr, host, dev, bad))
+            return fail(c, HB_EINVAL, "file " + std::to_string(bad) + ": invalid key");
+        unsigned long long qs[2 * HB_QSLOT];
+        auto launch = [&]() -> int {
+            CblkPrfArgs<NL> A;
+            memset(&A, 0, sizeof A);
+            A.prf = L.at<const PrfParams<NL>>(dev, HB_CBK_PRF);
+            A.files = L.at<const BatchFile>(dev, HB_CBK_FILES);
+            A.jobs = L.at<const HbCbJob>(dev, HB_CBK_JOBS);
+            A.njobs = T.nj;
+            A.idx = L.at<const u32>(dev, HB_CBK_IDX);
+            A.fv = L.at<u32>(dev, HB_CBK_FV);
+            A.araw = L.at<u32>(dev, HB_CBK_AM);
+            A.C = C;
+            A.S = S;
+            A.tw = pi.tw;
+            A.t0 = c->t0;
+            A.queue = c->queue;
+            // a workgroup per wave-job up to one per CU (cxx_encode_many_impl)
+            HB_CHECK(hb_launch_cblocks_prf<NL>(A, nr, batch_grid(c, T.nj), c->stream), "hb_cblocks_prf_kernel launch");
+            if (int rc = run_mont<NL>(c, p, A.araw, A.araw, G.nsegs * S)) return rc;
+            c->last_launches += 2;
+            if (T.nwg) {
+                BatchMacArgs<NL> M;
+                memset(&M, 0, sizeof M);
+                make_mod<NL>(p, M.mod);
+                M.files = A.files;
+                M.wgs = L.at<const BatchMacWg>(dev, HB_CBK_WGS);
+                M.fv = A.fv;
+                M.amont = A.araw;
+                M.C = C;
+                M.ss = pi.ss;
+                M.S = S;
+                M.tw = pi.tw;
+                HB_CHECK(hb_launch_batch_mac<NL>(M, (u32)T.nwg, c->stream), "hb_batch_mac_kernel launch");
+                c->last_launches += 1;
+            }
+            return 0;
+        };
+        // slots 0 (wave-job counter, F tries) and 1 (alpha tries)
+        if (int rc = group_transport(c, L, 2, launch, HB_CBK_TAGS, B.tags_dev ? nullptr : "hipMemcpyAsync(D2H tags)", qs,
+                                     "cxx listed-block encode"))
+            return rc;
+        tries += qs[1];
+        if (!B.tags_dev) hb_blocks_tags_out(files, plan.blk, G, B, host);
+        return 0;
+    };
+
+    int rc = 0;
+    for (size_t g = 0; g < plan.blk.groups.size() && !rc; ++g) rc = run_group(g);
+    rc = batch_finish(c, rc, true, 2, std::vector<u64>(), false, [](u64) -> int { return 0; });
     if (rc) return rc;
     if (tries_out) *tries_out = tries;
     return 0;
@@ -4880,6 +4973,33 @@ int hb_cxx_encode_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t se
     return by_nl(c, pi.nl, [&](auto NL) {
         return cxx_encode_many_impl<HB_NL(NL)>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
     });
+}
+
+int hb_cxx_encode_blocks_many(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors, size_t key_len,
+                              const hb_blocks_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {
+    if (!c) return HB_EINVAL;
+    PrimeInfo pi;
+    if (int rc = entry_begin(c, p_be, p_len, pi, key_len, key_len, sectors, flags, HB_DATA_ON_DEVICE | HB_TAGS_ON_DEVICE,
+                             "hb_cxx_encode_blocks_many takes HB_DATA_ON_DEVICE and HB_TAGS_ON_DEVICE only"))
+        return rc;
+    if (tries_out) *tries_out = 0;
+    if (nfiles == 0) return 0;
+    if (!files) return fail(c, HB_EINVAL, "files is NULL");
+    std::string msg;
+    if (int rc = hb_cblocks_check(files, nfiles, (u64)pi.ss * sectors, msg)) return fail(c, rc, msg);
+    if (pi.tw % 16 != 0 || pi.tw > 4u * (u32)pi.nl)
+        return fail(c, HB_EUNSUPPORTED, "cxx prf mode needs ByteCount(p) to be a multiple of 16");
+    HB_CHECK(hipSetDevice(c->device), "hipSetDevice");
+    return by_nl(c, pi.nl, [&](auto NL) {
+        return cxx_encode_blocks_impl<HB_NL(NL)>(c, p_be, p_len, pi, sectors, key_len, files, nfiles, flags, tries_out);
+    });
+}
+
+int hb_cxx_encode_blocks(hb_ctx *c, const uint8_t *p_be, size_t p_len, uint32_t sectors, const uint8_t *f_key,
+                         const uint8_t *alpha_key, size_t key_len, const uint64_t *indices, uint64_t nblocks,
+                         const uint8_t *data, uint64_t len, uint8_t *tags, uint32_t flags, uint64_t *tries_out) {
+    const hb_blocks_desc D = {f_key, alpha_key, indices, nblocks, data, len, tags};
+    return hb_cxx_encode_blocks_many(c, p_be, p_len, sectors, key_len, &D, 1, flags, tries_out);
 }
 
 int hb_encode_mixed(hb_ctx *c, const hb_encode_mixed_desc *files, uint64_t nfiles, uint32_t flags, uint64_t *tries_out) {

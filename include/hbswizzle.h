@@ -128,7 +128,7 @@ const char *hb_build_flags_string(void);
 #define HB_SW_WIDE_SYNC_ALPHA 2097152u /* HB_WIDE_SYNC_ALPHA: the split encode computes alpha and its digit table on the compute stream, before the PRF passes, instead of beside them */
 #define HB_SW_QCHUNK 4194304u       /* HB_QCHUNK=n: jobs per queue refill in the encode engines (default 256 up to 256-bit primes, 64 above; rounded up to a multiple of 64) */
 #define HB_SW_DIGEST_CACHE 8388608u  /* HB_DIGEST_CACHE_MIB=n: cap of the context's digest table in MiB for this call, over hb_ctx_set_digest_cache's (0: no table) */
-#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode; hb_encode_blocks_many puts at most n listed blocks into one group and continues a longer list in the next */
+#define HB_SW_BATCH_BLOCKS 16777216u  /* HB_TEST_BATCH_BLOCKS=n: hb_encode_many and hb_cxx_encode_many put at most n blocks into one group of launches, and files of more than n blocks go to the single-file encode; hb_encode_blocks_many and hb_cxx_encode_blocks_many put at most n listed blocks into one group and continue a longer list in the next */
 #define HB_SW_BATCH_CHUNKS 33554432u  /* HB_TEST_BATCH_CHUNKS=n: hb_verify_rhs_many, hb_prove_many and their cxx counterparts put at most n challenge indices into one group of launches, and proofs of more than n chunks go to the single verify / prove */
 uint32_t hb_test_switches(void);
 
@@ -548,6 +548,54 @@ int hb_encode_blocks(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t se
 int hb_cxx_encode_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
                        size_t key_len, const hb_file_desc *files, uint64_t nfiles,
                        uint32_t flags, uint64_t *tries_out);
+
+/* hb_encode_blocks_many for the cxx Swizzle (heartbeat.Heartbeat): the tags of
+ * listed blocks -- those an edit or an append changed -- of one file or of
+ * many files each under its own keys, in one call, under the file's existing
+ * keys.  Same descriptors as hb_encode_blocks_many (hb_blocks_desc).
+ * Replaces a caller's loop over the body of cxx/shacham_waters_private.cxx:674-694
+ * for chosen values of i: tags[k] of a file are exactly the bytes that
+ * hb_encode writes with HB_PRF_CXX for block_base = indices[k], data + k*C,
+ * len_k = min(C, len - k*C) and nblocks = 1, with C = sectors * ss.  Only the
+ * last listed block may be short; when it is empty it reads no sector and its
+ * tag is F(indices[k]) as the prf returned it, without `%= p` (:681-690).
+ * indices may come in any order and may repeat.  One prime, one `sectors` and
+ * one key_len for the batch.  A group of lists is one copy up (key schedules,
+ * u32 indices and host data together), one PRF launch (one lane per
+ * evaluation, wave-jobs of up to 64 evaluations of one list under one key: F
+ * at the listed indices and alpha_j of every file), one Montgomery pass over
+ * the group's alpha values, hb_encode_many's MAC launch over the packed blocks
+ * that read a sector, and one copy down; the runtime splits a call, and a
+ * single list, whose device scratch would pass the batches' cap
+ * ($HB_TEST_BATCH_BLOCKS: at that many listed blocks), and nothing goes
+ * through the single encode.
+ * Everything is checked before any GPU work, no tag buffer is written on a
+ * failure, and the checks run in this order:
+ *   1. the context, the prime, key_len (16, 24 or 32), sectors > 0;
+ *   2. flags: anything but HB_DATA_ON_DEVICE / HB_TAGS_ON_DEVICE (device
+ *      pointers of any alignment) returns HB_EUNSUPPORTED;
+ *   3. nfiles == 0 returns HB_OK; then files == NULL is HB_EINVAL;
+ *   4. every descriptor as hb_encode_blocks_many checks it -- per file keys,
+ *      indices, len, tags, data; the first fault of the first faulty file --
+ *      with HB_EINVAL and "file N: ...";
+ *   5. every index, file by file: one of 2^32 or above returns
+ *      HB_EUNSUPPORTED with "file N: index ..." (the reference's chunk_id is
+ *      an unsigned int and the cxx prove refuses 2^32 tags; a wrapped index
+ *      would collide silently);
+ *   6. a prime whose ByteCount is not a multiple of 16: HB_EUNSUPPORTED, as
+ *      hb_encode(HB_PRF_CXX).
+ * A file with nblocks == 0 is a no-op.  *tries_out (may be NULL) receives the
+ * sum of the listed blocks' F tries: what those single hb_encode calls report
+ * in total. */
+int hb_cxx_encode_blocks_many(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                              size_t key_len, const hb_blocks_desc *files, uint64_t nfiles,
+                              uint32_t flags, uint64_t *tries_out);
+
+/* hb_cxx_encode_blocks_many for one file (nfiles = 1; errors read "file 0: ..."). */
+int hb_cxx_encode_blocks(hb_ctx *ctx, const uint8_t *p_be, size_t p_len, uint32_t sectors,
+                         const uint8_t *f_key, const uint8_t *alpha_key, size_t key_len,
+                         const uint64_t *indices, uint64_t nblocks, const uint8_t *data, uint64_t len,
+                         uint8_t *tags, uint32_t flags, uint64_t *tries_out);
 
 /* The cxx prf, prf::evaluate(i) (cxx/prf.hxx:125-145), for n unsigned-int
  * inputs, keyed by key and bounded by limit (any limit up to 2048 bits; when
